@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising steps/sec of the InstanceDiff sampling loop on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line.  Everything else
+the line can carry -- the per-kernel roofline pass, the training leg, the CPU baseline -- runs only with --full (each of them can then
+still be left out with its --no-* switch).
 
 N > 1: one rank per GPU.  Under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) the process IS
 a rank; started plainly (`python bench.py --gpus N`, the reference's one-command launch: README.md:35, trainUM.py:50-66) the parent
@@ -14,7 +18,8 @@ noise_net, each with its 4 ScoreMapModules and single-token image-context cross-
 update, fp32, random-init weights (seed 0), inputs resident in HBM, on-device Philox noise.  Multi-GPU = N
 independent replicas (sampling shards by image, no data-path collective) -> weak scaling.
 
-Prints ONE JSON line: metric/value/... plus
+Prints ONE JSON line: metric/value/... plus (roofline, cpu_baseline, train and launches_per_step with --full only; a plain run reports
+them as null / "skipped")
   roofline     : dominant kernel = the Winograd conv kernel with the largest share of the step (`kernels` lists all three: the
                  F(4x4,3x3) kernels conv_wino4_kernel / conv_wino4h_kernel and the F(2x2,3x3) conv_wino_kernel).  `achieved` = the matrix-core FLOP the kernel's algorithm EXECUTES per
                  launch (36 multiply-adds per 4x4 output tile and channel pair = 1/4 of the direct form; F(2x2,3x3): 16/36) /
@@ -52,12 +57,16 @@ def parse():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the per-kernel roofline "
+                    "pass, the training leg (BASELINE c3) and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its "
+                    "last step (the denoising state x a caller of the loop receives) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-batch", type=int, default=0, help="images per CPU-baseline step (0 = the full batch when one step "
                     "is estimated to fit --cpu-budget-s, else 4)")
     ap.add_argument("--cpu-budget-s", type=float, default=140.0, help="time budget of the CPU-baseline leg (warm + timed steps)")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the `train` key of the default line (BASELINE c3 at N=1, ~40 s)")
+    ap.add_argument("--no-train-leg", action="store_true", help="with --full: skip the `train` key of the line (BASELINE c3 at N=1, ~40 s)")
     ap.add_argument("--attn", choices=["f32", "bf16", "f16"], default="f32", help="bf16 / f16 = REDUCED-PRECISION VARIANT line (self-attention "
                     "contractions on the bf16 / fp16 matrix cores; f16 with operands clamped to +-255 is the reference's own form, BASELINE "
                     "config c5): own metric label, PSNR delta vs the fp32 path stated")
@@ -65,7 +74,10 @@ def parse():
     ap.add_argument("--mode", choices=["sample", "train", "irsde"], default="sample",
                     help="sample = headline denoising-steps/s metric (driftSDE: 2 UNet forwards + update per step); train = secondary "
                          "training-iterations/s line; irsde = secondary line for the IRSDE single-network loop (1 UNet forward + reverse_sde_step)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.mode == "train":
+        ap.error("--dump-outputs covers the sampling loops (--mode sample / irsde)")
+    return args
 
 
 def spawn_ranks(n, cmd, env=None, poll_s=0.2):
@@ -354,6 +366,24 @@ def log(msg):
 
 _T0 = time.time()
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (a device tensor) to DIR/<name>.npy as float32, within 64 MB together: an array too large for its
+    share is written as a fixed sample (seed 0, sorted flat indices, which go to DIR/<name>_index.npy as float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share // 12].sort().values
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.double().numpy())
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.numpy())
+    log("outputs of the last timed step written to %s: %s" % (dirname, ", ".join(sorted(arrays))))
+
 
 def train_roofline(it, iters=2):
     """Per-kernel-class roofline of the training iteration, measured live: `iters` more iterations on ONE stream with HIP events on the
@@ -518,7 +548,7 @@ def train_measure(args, world, rank, dev, batch_size, steps, warmup, wire=None, 
 def train_bench(args, world, rank, dev):
     """Secondary line (BASELINE config c3): training iterations/sec of CLIPDriftModel.optimize_parameters."""
     import torch.distributed as dist
-    m = train_measure(args, world, rank, dev, args.batch, args.steps, args.warmup, roofline=not args.no_roofline)
+    m = train_measure(args, world, rank, dev, args.batch, args.steps, args.warmup, roofline=args.full and not args.no_roofline)
     el, loss = m["el"], m["loss"]
     if rank == 0:
         value = world * args.steps / el
@@ -612,7 +642,8 @@ def train_dryrun(args, world, rank):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend="gloo", rank=rank, world_size=world)
     ok_all, legs = True, {}
-    wires = [args.grad_wire] if args.mode == "train" else ["fp32", "bf16"]  # the default line's training leg reports both
+    # the default line's training leg (--full) reports both wires; a plain default line has none
+    wires = [args.grad_wire] if args.mode == "train" else ["fp32", "bf16"] if args.full else []
     for wire in wires:
         os.environ["IDIFF_GRAD_WIRE"] = wire
         torch.manual_seed(1000 + rank)  # ranks start from DIFFERENT weights: the broadcast must make them equal
@@ -641,12 +672,17 @@ def train_dryrun(args, world, rank):
                       "exchange": {"wire": wire, "span_ms": tm[0]["span_ms"] if tm else None, "exposed_ms": tm[0]["exposed_ms"] if tm else None}}
         ok_all = ok_all and ok
     if rank == 0:
-        note = "no GPU: rendezvous + model build + parameter broadcast + flat gradient all-reduce only"
+        note = ("no GPU: rendezvous + model build + parameter broadcast + flat gradient all-reduce only" if wires else
+                "no GPU: rendezvous only (the training leg runs with --full)")
         if args.mode == "train":
             leg = legs[args.grad_wire]
             print(json.dumps({"metric": "training iterations/sec (%dx%d bs%d/GPU)" % (args.size, args.size, args.batch), "value": None,
                               "dryrun": note, "n_gpus": world, "grad_wire": args.grad_wire, "grad_sync_ok": leg["grad_sync_ok"],
                               "flat_gradient_floats": leg["flat_gradient_floats"], "scale": leg["scale"], "exchange": leg["exchange"]}), flush=True)
+        elif not args.full:
+            print(json.dumps({"metric": "denoising steps/sec (%dx%d bs%d)" % (args.size, args.size, args.batch), "value": None, "dryrun": note,
+                              "n_gpus": world, "config": {"parallelism": "replicas x%d (no collective)" % world},
+                              "train": "skipped (--full not given)"}), flush=True)
         else:
             n1, src = stored_n1_train()
             train = dict(legs["fp32"], n_gpus=world, batch_per_gpu=32, it_per_s=None, n1_it_per_s=n1, n1_source=src,
@@ -704,6 +740,8 @@ def irsde_bench(args, world, rank, dev):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         el = float(tmax.item())
     assert torch.isfinite(state["x"]).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": state["x"]})
     if rank == 0:
         value = world * args.steps / el
         print(json.dumps({"metric": "IRSDE denoising steps/sec (%dx%d bs%d)" % (args.size, args.size, args.batch), "value": round(value, 4),
@@ -791,11 +829,13 @@ def main():
         el = float(tmax.item())
     assert torch.isfinite(run.x).all(), "non-finite state after the timed steps"
     log("timed region: %.3f s for %d steps" % (el, args.steps))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": run.x})  # before the roofline pass, which steps the same state further
 
     roof = None
     launches_per_step = None
     graph_mode = run.stepper.mode == "graph"
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # second pass over the same K steps, on ONE stream (the timed region overlaps the two nets on two streams, which
         # would smear per-launch event times), every conv launch bracketed by HIP events on its launch stream
         two = sde.two_streams
@@ -857,8 +897,10 @@ def main():
         barrier()
 
     default_workload = args.size == 256 and args.batch == 16 and variant is None
+    train_skip = ("--full not given" if not args.full else "--no-train-leg" if args.no_train_leg
+                  else None if default_workload else "not the default 256x256 batch-16 fp32 line")
     train_ranks = None
-    if world > 1 and default_workload and not args.no_train_leg:
+    if world > 1 and train_skip is None:
         # BASELINE c3 -- the one configuration with an exchange step -- across the ranks of THIS run: every rank takes part (the RCCL
         # all-reduce of the flat gradient buffers is collective); rank 0 reports it under "train"
         log("train leg across %d ranks (BASELINE c3: flat RCCL all-reduce under the backward) ..." % world)
@@ -876,9 +918,9 @@ def main():
         # it read 4-5 % low (3.75 against 3.91-3.98 it/s, profiles/r04/README.md)
         train = None
         if world > 1:
-            train = train_ranks if train_ranks is not None else "skipped (%s)" % ("--no-train-leg" if args.no_train_leg else "not the default 256x256 batch-16 fp32 line")
-        elif args.no_train_leg or not default_workload:
-            train = "skipped (%s)" % ("--no-train-leg" if args.no_train_leg else "not the default 256x256 batch-16 fp32 line")
+            train = train_ranks if train_ranks is not None else "skipped (%s)" % train_skip
+        elif train_skip is not None:
+            train = "skipped (%s)" % train_skip
         else:
             log("train leg (BASELINE c3 at N=1) ...")
             try:
@@ -888,7 +930,7 @@ def main():
             except Exception as e:  # a reported side measurement; never hide the headline
                 train = {"error": repr(e)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other ranks of a multi-GPU run must not wait on it
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other ranks of a multi-GPU run must not wait on it
             log("cpu baseline (oracle) ...")
             try:
                 cpu = cpu_baseline(args, batch)
@@ -909,7 +951,7 @@ def main():
                                           "fp32-class result (2e-6 vs fp64, tests/test_ops_gpu.py); f32 MFMA where the pixels do not tile by 256",
                                "attention": "f32 MFMA" if variant is None else "%s MFMA self-attention (operands clamped to +-255 for f16), fp32 softmax" % args.attn,
                                "groupnorm_statistics": "fp32 partials, fp64 fixed-order reduce", "sde_update": "f32 (one rounding per op)"},
-                "two_streams": bool(sde.two_streams), "variant": variant,
+                "two_streams": bool(sde.two_streams), "variant": variant, "full": args.full,
                 "launches_per_step": launches_per_step,
                 "config": {"workload": "%dx%d 1-ch synthetic, %d-step reverse chain, batch %d per GPU, 2 UNet fwd + reverse update per step"
                                        % (args.size, args.size, args.T, args.batch),

@@ -438,15 +438,15 @@ def test_fused_adam_zero_grad_honours_set_to_none():
 
 
 def test_bench_default_line_carries_the_training_exchange_at_world_2(tmp_path):
-    """`python bench.py --gpus 2` -- the command the driver's scaling run issues -- must put the collective into ITS line: the default
-    mode's N > 1 path runs BASELINE c3 across the ranks (train_leg_ranks) and reports it under "train" with the exchange measured for
-    the fp32 wire and the bf16 wire variant.  Without a GPU the dry run goes through the same rendezvous / GradSync / timing-mark code
-    for both wires and prints the line's shape (no rates)."""
+    """`python bench.py --gpus 2 --full` must put the collective into ITS line: the default mode's N > 1 path runs BASELINE c3 across
+    the ranks (train_leg_ranks) and reports it under "train" with the exchange measured for the fp32 wire and the bf16 wire variant.
+    Without a GPU the dry run goes through the same rendezvous / GradSync / timing-mark code for both wires and prints the line's shape
+    (no rates)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(IDIFF_BENCH_DRYRUN="1", OMP_NUM_THREADS="2")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env, capture_output=True,
-                       text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], env=env,
+                       capture_output=True, text=True, timeout=900)
     if torch.cuda.is_available():
         pytest.skip("dry run is the no-GPU hook; on a GPU box the rehearsal (IDIFF_BENCH_REHEARSAL=1) runs the real step")
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
@@ -457,6 +457,27 @@ def test_bench_default_line_carries_the_training_exchange_at_world_2(tmp_path):
         assert leg["grad_sync_ok"] is True and leg["grad_wire"] == wire and leg["scale"] == 0.5 and leg["flat_gradient_floats"] > 60e6
         ex = leg["exchange"]
         assert ex["wire"] == wire and ex["span_ms"] >= ex["exposed_ms"] >= 0.0
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_what_exceeds_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: an array within its share of the limit is written whole as float32 with its shape; a larger one as a fixed
+    sample (the same indices every run, stored next to it) that keeps the files within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.randn(2, 1, 8, 8, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x})
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 1, 8, 8) and np.array_equal(got, x.float().numpy())
+    assert not (tmp_path / "a" / "x_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 12000)
+    y = torch.randn(4, 1, 32, 32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": y})
+    vals, idx = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "x_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape == (1000,)
+    assert vals.nbytes + idx.nbytes <= 12000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(vals, y.reshape(-1).numpy()[idx.astype(np.int64)])
+    assert np.array_equal(vals, np.load(tmp_path / "c" / "x.npy")) and np.array_equal(idx, np.load(tmp_path / "c" / "x_index.npy"))
 
 
 def test_grad_sync_timing_marks_cover_one_step_per_finish():
