@@ -105,6 +105,16 @@ typedef struct {
                                With it, 1x1 layers whose pixels tile by 256 (Cout % 64 == 0, C0 % 8 == 0, Cin % 8 == 0, Cin >= 32, no prologue, no
                                statistics) run on the bf16 matrix cores with six products per fp32 product (IDIFF_CONV_ALGO_X3:
                                fp32-class result, csrc/conv1x1_x3.hip); NULL keeps them on the f32 matrix cores */
+    /* ---- opt-in REDUCED-PRECISION 3x3 convs (IDIFF_CONV_ALGO_BF16, csrc/conv_bf16.hip, conv_bf16_wgrad.hip).  Both fields zero (the
+       default) = the fp32 behaviour above, unchanged.  Numerics contract of the bf16 mode: every gathered input operand is computed in
+       fp32 exactly as the f32 kernels compute it (virtual concat, nearest x2 upsample, prologue affine + SiLU, then zero padding); each
+       operand and each weight is then rounded once to bf16 (round to nearest even, a plain cast); the products are summed in fp32 on
+       the bf16 matrix cores; everything after the sum (bias, GroupNorm partials, vec, residual, aux term) is the fp32 epilogue.
+       Eligible layers: ks == 3, NORMAL or UPSAMPLE2, Cout % 64 == 0, C0 % 32 == 0, C1 % 32 == 0, Hout % 8 == 0, Wout % 32 == 0;
+       any other layer keeps the fp32 kernels (idiff_conv2d_last_algo says which ran). */
+    const void* wbf16;      /* image of idiff_pack_conv_weight_bf16 (16-byte aligned; transpose = 1 for the data-gradient conv) */
+    int32_t operands;       /* 0 = fp32 operands; 1 = bf16 operands on eligible 3x3 layers: the forward takes IDIFF_CONV_ALGO_BF16
+                               when wbf16 is set too; idiff_conv2d_wgrad takes its bf16 form (the weight gradient needs no image) */
 } idiff_conv_desc;
 
 int idiff_conv2d_num_tiles(int Hout, int Wout);
@@ -116,6 +126,7 @@ int idiff_conv2d_fwd(const idiff_conv_desc* d, idiff_stream_t stream);
 #define IDIFF_CONV_ALGO_WINOGRAD4 3 /* F(4x4,3x3),  conv_wino4.hip  */
 #define IDIFF_CONV_ALGO_WINOGRAD4H 4 /* F(4x4,3x3), half-patch items, two workgroups per CU: conv_wino4h.hip */
 #define IDIFF_CONV_ALGO_X3 5 /* 1x1, fp32 operands as three bf16 planes, six bf16 MFMAs per product: conv1x1_x3.hip */
+#define IDIFF_CONV_ALGO_BF16 6 /* 3x3, operands rounded to bf16, fp32 sums (opt-in, idiff_conv_desc.operands): conv_bf16.hip */
 int idiff_conv2d_last_algo(void);
 /* Which kernel idiff_conv2d_fwd(d, .) WOULD launch for this descriptor: every check and selection rule of the call, no launch
  * (IDIFF_CONV_ALGO_* >= 0, or IDIFF_E_*).  The weight-image pointers of `d` only have to point at memory of the right size: a
@@ -141,6 +152,12 @@ int idiff_pack_conv_weight_wino(const float* w, float* wwino, int Cout, int Cin,
  * [Cin/4][ceil(Cout/64)][9 position quads][4 co-blocks][4 k][16 co][4]  (36*Cin*ceil(Cout/64)*64 floats; Cin % 8 == 0,
  * Cout % 16 == 0: a partial last block is zero-filled) -- an opaque image, only idiff_conv2d_fwd reads it. */
 int idiff_pack_conv_weight_wino4(const float* w, float* wwino4, int Cout, int Cin, int transpose, idiff_stream_t stream);
+/* 3x3 weights w [Cout][Cin][3][3] (torch layout) -> the bf16 image idiff_conv_desc.wbf16 points to, each weight rounded once to
+ * bf16 (nearest even): [chunk of 32 ci][block of 64 co][tap][octet of 8 ci][co][8 bf16] of the conv's (Cout, Cin), zero beyond them.
+ * transpose != 0: the flipped, in/out-swapped weights of the data-gradient conv (the conv's Cout' = Cin, Cin' = Cout).  `image` holds
+ * idiff_conv_weight_bf16_bytes(Cout, Cin, transpose) bytes, 16-byte aligned. */
+long long idiff_conv_weight_bf16_bytes(int Cout, int Cin, int transpose);
+int idiff_pack_conv_weight_bf16(const float* w, void* image, int Cout, int Cin, int transpose, idiff_stream_t stream);
 /* Layers with fewer than 16 items PER SAMPLE (16x32 pixels x 64 output channels each) stay on the F(2x2,3x3) kernel; the batch
  * size never enters the choice (a sample's bits do not depend on its batch).  There is no process-wide switch: a caller that
  * wants another kernel for ONE call says so in idiff_conv_desc.algo_request. */
@@ -472,6 +489,9 @@ int idiff_mix3_per_sample(const float* x0, const float* cond, const float* eps, 
 int64_t idiff_conv2d_wgrad_ws_floats(const idiff_conv_desc* d);
 int idiff_conv2d_wgrad(const idiff_conv_desc* d, const float* dy, int64_t dy_bstride, float* dw, int accumulate, float* ws,
                        idiff_stream_t stream);
+/* With d->operands == 1 an eligible 3x3 layer (the shapes of IDIFF_CONV_ALGO_BF16) takes the bf16-operand form:
+ *   dW = sum bf16(dY) * bf16(X~), summed in fp32; per-(sample, block of up to 16 8x32 patches) partials reduced in sample / block order,
+ *   no atomics: bitwise reproducible, independent of the grid.  last_algo = IDIFF_CONV_ALGO_BF16. */
 /* IDIFF_CONV_ALGO_* of the calling thread's last idiff_conv2d_wgrad: the Winograd form (conv_wino_wgrad.hip) takes 3x3
  * layers with Cout % 64 == 0, Cin % 16 == 0 (C0 % 64 == 0 with a second source), Hout % 2 == 0, Wout % 16 == 0 */
 int idiff_conv2d_wgrad_last_algo(void);

@@ -69,4 +69,10 @@ int launch_conv_wino4h(const ConvArgs& a, int mode, hipStream_t st);
 bool conv1x1_x3_eligible(const ConvArgs& a, int mode);
 int launch_conv1x1_x3(const ConvArgs& a, int mode, const void* wx3, hipStream_t st);
 
+// conv_bf16.hip: the opt-in bf16-operand 3x3 conv (idiff_conv_desc.operands == 1): ks == 3, NORMAL / UPSAMPLE2, Cout % 64 == 0,
+// C0 % 32 == 0, C1 % 32 == 0, Hout % 8 == 0, Wout % 32 == 0, a 16-byte aligned image of idiff_pack_conv_weight_bf16.  `a` carries
+// conv_igemm.hip's geometry of 8x32-pixel patches and 64-channel blocks.
+bool conv_bf16_eligible(const ConvArgs& a, int ks, int mode, const void* wbf16);
+int launch_conv_bf16(const ConvArgs& a, int mode, const void* wbf16, hipStream_t st);
+
 }  // namespace idiff_detail

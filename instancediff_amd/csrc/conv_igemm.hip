@@ -691,8 +691,22 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
     const bool hard = d->algo_request > 0;
     const int req = (hard ? d->algo_request : -d->algo_request) - 1;  // -1: the library picks
     IDIFF_CHECK_ARG(req == -1 || req == IDIFF_CONV_ALGO_DIRECT || req == IDIFF_CONV_ALGO_WINOGRAD || req == IDIFF_CONV_ALGO_WINOGRAD4 ||
-                        req == IDIFF_CONV_ALGO_WINOGRAD4H || req == IDIFF_CONV_ALGO_X3,
+                        req == IDIFF_CONV_ALGO_WINOGRAD4H || req == IDIFF_CONV_ALGO_X3 || req == IDIFF_CONV_ALGO_BF16,
                     "conv2d: bad algo_request %d", d->algo_request);
+    IDIFF_CHECK_ARG(d->operands == 0 || d->operands == 1, "conv2d: bad operands %d", d->operands);
+    // Opt-in bf16 operands (conv_bf16.hip): only when the caller asks for them (operands == 1 with an image, or by name), on the 3x3 layers
+    // that tile for the kernel; every other layer keeps the fp32 choice below.
+    {
+        const bool reqbf = req == IDIFF_CONV_ALGO_BF16;
+        const bool can = idiff_detail::conv_bf16_eligible(a, d->ks, d->mode, d->wbf16);
+        IDIFF_CHECK_ARG(!(hard && reqbf) || can, "conv2d: algo_request bf16 but the layer is not a 3x3 that tiles for it (Cout %% 64, C0 / C1 %% 32, "
+                        "Hout %% 8, Wout %% 32) or has no bf16 image");
+        if (can && (reqbf || (req == -1 && d->operands == 1))) {
+            g_last_algo = IDIFF_CONV_ALGO_BF16;
+            if (plan) return IDIFF_OK;
+            return finalize_after(idiff_detail::launch_conv_bf16(a, d->mode, d->wbf16, st));
+        }
+    }
     // Flattened 1x1 layers with a split weight image: the bf16x3 kernel (conv1x1_x3.hip) -- fp32-class result at 2.67x the matrix
     // throughput; decided on the layer's shape only.  IDIFF_X3=0 (A/B runs) keeps them on the f32 matrix cores.
     {

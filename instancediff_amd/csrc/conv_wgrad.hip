@@ -427,11 +427,16 @@ extern "C" int64_t idiff_conv2d_wgrad_ws_floats(const idiff_conv_desc* d) {
     const int Hout = d->mode == IDIFF_CONV_UPSAMPLE2 ? d->Hin * 2 : (d->mode == IDIFF_CONV_UNSHUFFLE2 ? d->Hin / 2 : d->Hin);
     const int Wout = d->mode == IDIFF_CONV_UPSAMPLE2 ? d->Win * 2 : (d->mode == IDIFF_CONV_UNSHUFFLE2 ? d->Win / 2 : d->Win);
     int ck, nch, ncob, nt, tx, ns;
+    long long bf16_ws = 0;
     wg_geometry(d->ks, Cin, d->Cout, d->B, Hout, Wout, &ck, &nch, &ncob, &nt, &tx, &ns);
     if (d->ks == 1 && d->Cout % 64 == 0 && ((long long)Hout * Wout) % W1_PX == 0) {  // the streaming 1x1 kernel's split count
         int wcob, wcib, wns;
         wgrad1x1_geometry(Cin, d->Cout, d->B, Hout * Wout, &wcob, &wcib, &wns);
         if (wns > ns) ns = wns;
+    }
+    if (d->operands == 1 && d->ks == 3 && (d->mode == IDIFF_CONV_NORMAL || d->mode == IDIFF_CONV_UPSAMPLE2) && d->Cout % 64 == 0 && Hout % 8 == 0 &&
+        Wout % 32 == 0) {  // the bf16-operand form: its own partials
+        bf16_ws = idiff_detail::bf16_wgrad_ws_floats(Cin, d->Cout, d->B, Hout, Wout);
     }
     if (d->ks == 3 && d->Cout % 64 == 0) {  // the Winograd kernels may take this shape with their own split counts
         int wcob, wcib, wns;
@@ -442,7 +447,8 @@ extern "C" int64_t idiff_conv2d_wgrad_ws_floats(const idiff_conv_desc* d) {
             if (wns > ns) ns = wns;
         }
     }
-    return (int64_t)ns * d->ks * d->ks * Cin * d->Cout;
+    const int64_t f32_ws = (int64_t)ns * d->ks * d->ks * Cin * d->Cout;
+    return bf16_ws > f32_ws ? bf16_ws : f32_ws;
 }
 
 extern "C" int idiff_conv2d_wgrad(const idiff_conv_desc* d, const float* dy, int64_t dy_bstride, float* dw, int accumulate, float* ws,
@@ -498,6 +504,11 @@ extern "C" int idiff_conv2d_wgrad(const idiff_conv_desc* d, const float* dy, int
     w.pro_a = a.pro_a, w.pro_b = a.pro_b, w.dy = a.dy, w.dybs = a.dybs, w.ws = a.ws;
     w.ups = d->mode == IDIFF_CONV_UPSAMPLE2 ? 1 : 0;
     g_last_wgrad_algo = IDIFF_CONV_ALGO_DIRECT;
+    IDIFF_CHECK_ARG(d->operands == 0 || d->operands == 1, "conv2d_wgrad: bad operands %d", d->operands);
+    if (d->operands == 1 && idiff_detail::bf16_wgrad_eligible(w, d->ks, d->mode)) {
+        g_last_wgrad_algo = IDIFF_CONV_ALGO_BF16;
+        return idiff_detail::launch_bf16_wgrad(w, dw, accumulate, st);
+    }
     if (idiff_detail::wino4_wgrad_eligible(w, d->ks, d->mode)) {
         g_last_wgrad_algo = IDIFF_CONV_ALGO_WINOGRAD4;
         idiff_detail::wino4_wgrad_geometry(w.Cin, w.Cout, w.B, w.Hout, w.Wout, &w.ncob, &w.ncib, &w.nsplit);

@@ -30,4 +30,10 @@ bool wino4_wgrad_eligible(const WwArgs& a, int ks, int mode);
 void wino4_wgrad_geometry(int Cin, int Cout, int B, int Hout, int Wout, int* ncob, int* ncib, int* nsplit);
 int launch_wino4_wgrad(const WwArgs& a, hipStream_t st);
 
+// conv_bf16_wgrad.hip: the bf16-operand weight gradient (idiff_conv_desc.operands == 1); same shapes as conv_bf16_eligible.  Its own
+// workspace layout [B * K-blocks per sample][Cout][Cin][3][3] (bf16_wgrad_ws_floats) and its own ordered reduction into dw.
+bool bf16_wgrad_eligible(const WwArgs& a, int ks, int mode);
+long long bf16_wgrad_ws_floats(int Cin, int Cout, int B, int Hout, int Wout);
+int launch_bf16_wgrad(const WwArgs& a, float* dw, int accumulate, hipStream_t st);
+
 }  // namespace idiff_detail

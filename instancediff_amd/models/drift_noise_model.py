@@ -62,12 +62,25 @@ class EMA(nn.Module):
         return self.ema_model(*a, **k)
 
 
+CONV_DTYPES = ("f32", "bf16")
+
+
+def parse_conv_dtype(value):
+    """model option conv_dtype -> "f32" | "bf16" (None = "f32"); anything else raises ValueError"""
+    if value is None:
+        return "f32"
+    v = str(value).strip().lower() if isinstance(value, str) else value
+    if v not in CONV_DTYPES:
+        raise ValueError(f"conv_dtype must be one of {CONV_DTYPES}, got {value!r}")
+    return v
+
+
 class CLIPDriftModel():
     def __init__(self, text_encoder_pretrain_path, drift_net_lr, noise_net_lr, weight_decay_drift, beta1, beta2, nepoch, eta_min,
                  dist=False, gpu=True, optimize_type='predict_noise', optimize_target='std', if_train=True, dnet_settings=None,
                  nnet_settings=None, drift_loss='l2', noise_loss='none', if_MultiScoreMap=False, score_map_ch_mult=[1, 1, 2, 4],
                  score_map_ngf=64, use_image_context=False, use_degra_context=False, CLIP_Type="CLIP", device=None, text_encoder=None,
-                 class_tokens=None, score_map_dropout=0.1, score_map_decoder="ContextDecoder", score_map_if_flash=False):
+                 class_tokens=None, score_map_dropout=0.1, score_map_decoder="ContextDecoder", score_map_if_flash=False, conv_dtype="f32"):
         """score_map_dropout: dropout of the ScoreMapModules' decoder blocks in training mode -- the reference builds them with
         ContextDecoder's default 0.1 (models/_modified_BiomedCLIP.py:1194-1201; drift_noise_model.py:110-112 passes no value);
         model option `score_map_dropout` overrides (0 = the deterministic training function of rounds 1-2).
@@ -75,7 +88,11 @@ class CLIPDriftModel():
         models/_modified_BiomedCLIP.py:552-590,1247-1308); model option of the same name.
         score_map_if_flash (with ContextDecoder_Hierachical): the decoder attentions in the reference's half-precision form
         (Attention_flash, :481-517; the reference class's default) -- a labelled reduced-precision variant, inference only; False =
-        fp32, what if_flash=False computes."""
+        fp32, what if_flash=False computes.
+        conv_dtype: operand precision of both nets' 3x3 convs, sampling and training -- "f32" (default, the parity path) or "bf16",
+        the labelled reduced-precision variant (operands and weights rounded once to bf16 after the fp32 gather, fp32 sums and epilogue;
+        csrc/conv_bf16.hip); model option of the same name.  Anything else raises ValueError."""
+        conv_dtype = parse_conv_dtype(conv_dtype)
         dnet_settings = dict(dnet_settings)
         nnet_settings = dict(nnet_settings)
         for s in (dnet_settings, nnet_settings):  # :58-61
@@ -123,6 +140,8 @@ class CLIPDriftModel():
                     m.set_class_tokens(class_tokens)
         self.drift_net = create_net(dnet_settings, CLIP_ScoreMapModule=self.drift_prompt).to(self.device)
         self.noise_net = create_net(nnet_settings, CLIP_ScoreMapModule=self.noise_prompt).to(self.device)
+        self.conv_dtype = conv_dtype
+        self.drift_net.conv_dtype = self.noise_net.conv_dtype = conv_dtype
         if self.drift_prompt is not None:
             self.dp_ema = EMA(self.drift_prompt, beta=0.995, update_every=10)
             self.np_ema = EMA(self.noise_prompt, beta=0.995, update_every=10)
@@ -367,5 +386,7 @@ def create_CLIPDriftModel(train_opt, model_opt, phase='train', **extra):  # :758
         kw.update(score_map_decoder=str(model_opt['score_map_decoder']))
     if model_opt.get('score_map_if_flash') is not None:
         kw.update(score_map_if_flash=bool(model_opt['score_map_if_flash']))
+    if model_opt.get('conv_dtype') is not None:
+        kw.update(conv_dtype=parse_conv_dtype(model_opt['conv_dtype']))
     kw.update(extra)
     return CLIPDriftModel(model_opt['text_encoder_pretrain_path'], **kw)

@@ -82,6 +82,10 @@ SMM_SIDE = bool(int(os.environ.get("IDIFF_SMM_SIDE", "0")))
 GROUPED_SMM = bool(int(os.environ.get("IDIFF_GROUPED_SMM", "1")))
 
 def packed(conv):
+    """cached weight images of a conv; under ops.conv_operands("bf16") a 3x3 conv gets a separate entry that also holds its bf16
+    image (packed at the first eager use, so a captured sampling step replays with it in place); other convs share the fp32 entry"""
+    if ops.current_conv_operands() == "bf16" and tuple(conv.weight.shape[2:]) == (3, 3):
+        return _PREP.get(("pk_bf16", conv), (conv.weight,), lambda: ops.pack_conv_weight(conv.weight.detach().contiguous(), bf16=True))
     return _PREP.get(("pk", conv), (conv.weight,), lambda: ops.pack_conv_weight(conv.weight.detach().contiguous()))
 
 
@@ -783,8 +787,15 @@ class LearnableForwardUNet_MultiScoreMap(nn.Module):
             return forward_train(self, x_a, x_b, t, names, text_encoder, image_context)
         return self.forward_infer(x_a, x_b, t, names, text_encoder, image_context)
 
+    # operand precision of the 3x3 convs: "f32" (default) or "bf16" (the labelled reduced-precision variant; model option conv_dtype)
+    conv_dtype = "f32"
+
     @torch.no_grad()
     def forward_infer(self, x_a, x_b, t, names, text_encoder, image_context=None):
+        with ops.conv_operands(self.conv_dtype):
+            return self._forward_infer(x_a, x_b, t, names, text_encoder, image_context)
+
+    def _forward_infer(self, x_a, x_b, t, names, text_encoder, image_context=None):
         dev = x_a.device
         B, _, H, W = x_a.shape
         if not torch.is_tensor(t):

@@ -377,6 +377,12 @@ def forward_train(net, x_a, x_b, t, names, text_encoder, image_context=None):
     if any(m.context_decoder.if_flash for m in net.score_map_modules()):
         raise RuntimeError("score_map_if_flash (the fp16 form of the ScoreMapModule decoder attentions) is an inference-only variant: "
                            "no backward is built for it")
+    # the conv Functions record the operand precision at forward time and hand it to their backward
+    with ops.conv_operands(getattr(net, "conv_dtype", "f32")):
+        return _forward_train(net, x_a, x_b, t, names, text_encoder, image_context)
+
+
+def _forward_train(net, x_a, x_b, t, names, text_encoder, image_context=None):
     dev = x_a.device
     B, _, H, W = x_a.shape
     if not torch.is_tensor(t):

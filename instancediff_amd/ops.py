@@ -19,6 +19,8 @@ SDE_STEP, SDE_MEAN, SDE_ODE = 0, 1, 2
 PROFILE = None
 # tests set this to a collections.Counter: (algo, ks, Cin, Cout, Hout, Wout) -> calls, to assert which kernel served a layer
 ALGO_TRACE = None
+# the same for the weight gradients of the training path (train_ops.conv2d_wgrad; idiff_conv2d_wgrad_last_algo())
+WGRAD_TRACE = None
 
 
 def _stream():
@@ -67,7 +69,32 @@ WINOGRAD4_DGRAD = bool(int(os.environ.get("IDIFF_WINOGRAD4_DGRAD", "1")))
 
 
 CONV_ALGO_DIRECT, CONV_ALGO_WINOGRAD, CONV_ALGO_STREAM1X1, CONV_ALGO_WINOGRAD4, CONV_ALGO_WINOGRAD4H, CONV_ALGO_X3 = 0, 1, 2, 3, 4, 5
+CONV_ALGO_BF16 = 6  # opt-in: 3x3 operands rounded to bf16, fp32 sums (conv_operands("bf16"))
 _ALGO_REQUEST = threading.local()
+CONV_OPERANDS = ("f32", "bf16")
+_OPERANDS = threading.local()
+
+
+@contextlib.contextmanager
+def conv_operands(kind):
+    """Scope (this thread only) of the operand precision of the 3x3 convs issued inside: "f32" (the default, the parity path) or
+    "bf16" -- the labelled reduced-precision variant (idiff_conv_desc.operands = 1): every gathered operand and weight is rounded once
+    to bf16 after the fp32 gather, the products are summed in fp32, the epilogue stays fp32.  Layers that do not tile for the bf16
+    kernel keep the fp32 kernels.  conv2d() and train_ops.conv2d_wgrad() read it; the training autograd Functions record it at forward
+    time and hand it to their backward explicitly (autograd may run the backward on another thread)."""
+    if kind not in CONV_OPERANDS:
+        raise ValueError(f"conv operands must be one of {CONV_OPERANDS}, got {kind!r}")
+    old = getattr(_OPERANDS, "kind", "f32")
+    _OPERANDS.kind = kind
+    try:
+        yield
+    finally:
+        _OPERANDS.kind = old
+
+
+def current_conv_operands():
+    """the conv_operands() scope of the calling thread: 'f32' or 'bf16'"""
+    return getattr(_OPERANDS, "kind", "f32")
 
 
 @contextlib.contextmanager
@@ -84,12 +111,15 @@ def request_conv3x3_algo(algo):
 
 
 # ---------------------------------------------------------------------------------------------------
-def _alloc_conv_images(w, transpose):
-    """The direct image and, as attributes, whichever other images the weight's shape admits -- allocated, not filled."""
+def _alloc_conv_images(w, transpose, bf16=False):
+    """The direct image and, as attributes, whichever other images the weight's shape admits -- allocated, not filled.
+    bf16: also the bf16 image of a 3x3 weight (.bf16, idiff_pack_conv_weight_bf16) for the conv_operands("bf16") mode."""
     lib = _lib.load()
     _c(w, "weight")
     co, ci, k, _ = w.shape
     out = torch.empty((k * k, co, ci) if transpose else (k * k, ci, co), device=w.device, dtype=torch.float32)
+    if bf16 and k == 3:
+        out.bf16 = torch.empty((lib.idiff_conv_weight_bf16_bytes(co, ci, 1 if transpose else 0) // 2,), device=w.device, dtype=torch.int16)
     if k == 3 and WINOGRAD and co % 8 == 0 and ci % 8 == 0 and (ci if transpose else co) % 16 == 0:
         # Winograd-domain copy rides along as an attribute; conv2d hands it to the C ABI (idiff_conv_desc.wwino)
         cconv, kconv = (ci, co) if transpose else (co, ci)  # the conv's (Cout, Cin); Cout is padded to whole 64-blocks
@@ -120,12 +150,14 @@ def _fill_conv_images(out, w, transpose, algo=None):
         cconv1, kconv1 = (ci, co) if transpose else (co, ci)
         wm = w.reshape(co, ci).t().contiguous() if transpose else w
         check(lib.idiff_pack_conv1x1_x3(_p(wm), out.x3.data_ptr(), cconv1, kconv1, _stream()), "pack_conv1x1_x3")
+    if hasattr(out, "bf16") and (algo is None or algo == CONV_ALGO_BF16):
+        check(lib.idiff_pack_conv_weight_bf16(_p(w), out.bf16.data_ptr(), co, ci, tr, _stream()), "pack_conv_weight_bf16")
 
 
-def pack_conv_weight(w, transpose=False):
+def pack_conv_weight(w, transpose=False, bf16=False):
     """[Cout,Cin,k,k] -> packed [k*k][Cin][Cout] (or the flipped/transposed pack for the data gradient), with the Winograd-domain /
-    split-bf16 images the shape admits as attributes (.wino, .wino4, .x3)."""
-    out = _alloc_conv_images(w, transpose)
+    split-bf16 images the shape admits as attributes (.wino, .wino4, .x3); bf16=True adds the bf16-operand image of a 3x3 weight (.bf16)."""
+    out = _alloc_conv_images(w, transpose, bf16)
     _fill_conv_images(out, w, transpose)
     return out
 
@@ -140,19 +172,30 @@ class LazyConvWeight:
 
 
 def conv2d(src0, wpk, bias, ks, Cout, src1=None, mode=CONV_NORMAL, pro=None, out=None, res=None, vec=None, aux=None,
-           want_stats=False, algo=None, gn=None):
+           want_stats=False, algo=None, gn=None, operands=None):
     """Implicit-GEMM conv.  pro=(a,b): per-(b,c) affine+SiLU applied to src0 while it is gathered;
     aux=(tensor,a,b): adds silu(a*tensor+b) in the epilogue.  Returns out or (out, stats).
     algo: None = the library picks; CONV_ALGO_x = that kernel or an error (idiff_conv_desc.algo_request).
     gn = dict(groups, gamma, beta, film=None, eps=1e-5, want_mean_rstd=False): the GroupNorm(+FiLM) finalize of this conv's
     statistics rides on the call (a finalize launch enqueued by the library behind the conv): returns (out, (a, b)) or
-    (out, (a, b, mean_rstd))."""
+    (out, (a, b, mean_rstd)).
+    operands: "f32" | "bf16" | None (= the calling thread's conv_operands() scope).  "bf16" on a 3x3 conv sets
+    idiff_conv_desc.operands = 1 and hands the weight's .bf16 image over (a LazyConvWeight gets one packed)."""
     lib = _lib.load()
     B, C0, Hin, Win = src0.shape
+    operands = current_conv_operands() if operands is None else operands
+    if operands not in CONV_OPERANDS:
+        raise ValueError(f"conv operands must be one of {CONV_OPERANDS}, got {operands!r}")
+    bf16 = operands == "bf16" and ks == 3
     lazy = wpk if isinstance(wpk, LazyConvWeight) else None
     if lazy is not None:
-        wpk = _alloc_conv_images(lazy.w, lazy.transpose)
+        wpk = _alloc_conv_images(lazy.w, lazy.transpose, bf16 or algo == CONV_ALGO_BF16)
     d = ConvDesc()
+    if bf16:
+        d.operands = 1
+    wb = getattr(wpk, "bf16", None)
+    if wb is not None and ks == 3:  # read only with operands = 1 or a request by name
+        d.wbf16 = wb.data_ptr()
     if algo is not None:
         d.algo_request = 1 + algo
     elif ks == 3 and getattr(_ALGO_REQUEST, "algo", None) is not None:

@@ -53,11 +53,17 @@ def _conv_desc(src0, src1, mode, ks, Cout, pro=None):
     return d
 
 
-def conv2d_wgrad(src0, src1, mode, ks, dy, Cin, pro=None, dw=None, accumulate=False):
-    """dW [Cout, Cin, ks, ks] of conv2d(src0 (+src1), mode, ks, pro) given dy."""
+def conv2d_wgrad(src0, src1, mode, ks, dy, Cin, pro=None, dw=None, accumulate=False, operands=None):
+    """dW [Cout, Cin, ks, ks] of conv2d(src0 (+src1), mode, ks, pro) given dy.  operands: "f32" | "bf16" | None (= the calling
+    thread's ops.conv_operands() scope); "bf16": dW = sum bf16(dY) * bf16(X~) in fp32 on the layers that tile for it."""
     lib = _lib.load()
     Cout = dy.shape[1]
+    operands = ops.current_conv_operands() if operands is None else operands
+    if operands not in ops.CONV_OPERANDS:
+        raise ValueError(f"conv operands must be one of {ops.CONV_OPERANDS}, got {operands!r}")
     d = _conv_desc(src0, src1, mode, ks, Cout, pro)
+    if operands == "bf16" and ks == 3:
+        d.operands = 1
     nws = lib.idiff_conv2d_wgrad_ws_floats(C.byref(d))
     ws = torch.empty((nws,), device=dy.device, dtype=torch.float32)
     if dw is None:
@@ -69,14 +75,19 @@ def conv2d_wgrad(src0, src1, mode, ks, dy, Cin, pro=None, dw=None, accumulate=Fa
         check(lib.idiff_conv2d_wgrad(C.byref(d), _p(dy), _bs(dy, "dy"), _p(_c(dw)), 1 if accumulate else 0, _p(ws), _stream()), "conv2d_wgrad")
     if pr.on:
         pr.rec["algo"] = lib.idiff_conv2d_wgrad_last_algo()
+    if ops.WGRAD_TRACE is not None:
+        ops.WGRAD_TRACE[(lib.idiff_conv2d_wgrad_last_algo(), ks, Cin, Cout, Hout, Wout)] += 1
     return dw
 
 
-def conv2d_dgrad(dy, weight, ks, mode, Cin_virtual, res=None):
-    """data gradient w.r.t. the (virtual) conv input: [B, Cin_v, Hout, Wout]; the caller undoes upsample/unshuffle."""
+def conv2d_dgrad(dy, weight, ks, mode, Cin_virtual, res=None, operands=None):
+    """data gradient w.r.t. the (virtual) conv input: [B, Cin_v, Hout, Wout]; the caller undoes upsample/unshuffle.
+    operands: as ops.conv2d (the autograd Functions pass what their forward ran with)."""
+    operands = ops.current_conv_operands() if operands is None else operands
     w = weight.detach().contiguous()
-    wT = ops.LazyConvWeight(w, transpose=True) if LAZY_PACK else ops.pack_conv_weight(w, transpose=True)  # packed at the call
-    return ops.conv2d(dy, wT, None, ks, Cin_virtual, res=res)
+    bf16 = operands == "bf16" and ks == 3
+    wT = ops.LazyConvWeight(w, transpose=True) if LAZY_PACK else ops.pack_conv_weight(w, transpose=True, bf16=bf16)  # packed at the call
+    return ops.conv2d(dy, wT, None, ks, Cin_virtual, res=res, operands=operands)
 
 
 def channel_sums(x, per_sample=False):
@@ -173,7 +184,7 @@ LAZY_PACK = os.environ.get("IDIFF_LAZY_PACK", "1") != "0"  # A/B runs: 0 = every
 
 def _packed(w):
     if not LAZY_PACK:
-        return ops.pack_conv_weight(w.detach().contiguous())
+        return ops.pack_conv_weight(w.detach().contiguous(), bf16=ops.current_conv_operands() == "bf16")
     return ops.LazyConvWeight(w.detach().contiguous())  # packed at the conv call: only the image the chosen kernel reads
 
 
@@ -186,6 +197,7 @@ class ConvFn(torch.autograd.Function):
         out = ops.conv2d(src0, _packed(weight), bias, ks, Cout, src1=src1, mode=mode, out=None if slot is None else slot.t)
         ctx.save_for_backward(src0, src1, weight)
         ctx.ks, ctx.mode, ctx.has_bias = ks, mode, bias is not None
+        ctx.operands = ops.current_conv_operands()  # the backward may run on another thread: no scope there
         return out
 
     @staticmethod
@@ -197,14 +209,14 @@ class ConvFn(torch.autograd.Function):
         C0 = src0.shape[1]
         d0 = d1 = None
         if ctx.needs_input_grad[0] or (src1 is not None and ctx.needs_input_grad[1]):
-            dxv = conv2d_dgrad(dout, weight, ks, mode, Cin)
+            dxv = conv2d_dgrad(dout, weight, ks, mode, Cin, operands=ctx.operands)
             if mode == ops.CONV_UPSAMPLE2:
                 dxv = sumpool2x2(dxv)
             elif mode == ops.CONV_UNSHUFFLE2:
                 dxv = pixel_shuffle2(dxv)
             d0 = dxv[:, :C0] if src1 is not None else dxv
             d1 = dxv[:, C0:] if src1 is not None else None
-        dw = conv2d_wgrad(src0, src1, mode, ks, dout, Cin) if ctx.needs_input_grad[2] else None
+        dw = conv2d_wgrad(src0, src1, mode, ks, dout, Cin, operands=ctx.operands) if ctx.needs_input_grad[2] else None
         db = channel_sums(dout) if ctx.has_bias and ctx.needs_input_grad[3] else None
         return d0, d1, dw, db, None, None, None
 
@@ -228,6 +240,7 @@ class ResBlockFn(torch.autograd.Function):
             out = ops.conv2d(src0, _packed(wr), br, 1, Co, src1=src1, aux=(h2, a2, c2), vec=vec, out=dst)
         ctx.save_for_backward(src0, src1, film, w1, g1, be1, w2, g2, be2, wr, h1, h2, a1, c1, mr1, a2, c2, mr2)
         ctx.groups, ctx.has_vec = groups, vec is not None
+        ctx.operands = ops.current_conv_operands()  # the backward may run on another thread: no scope there
         return out
 
     @staticmethod
@@ -243,18 +256,19 @@ class ResBlockFn(torch.autograd.Function):
         # 1x1 conv) come out of the GroupNorm backward's own passes: no plane_sum launch over those tensors
         dh2, dg2, dbe2, _, db2, dout_sums = gn_silu_bwd(dout, h2, a2, c2, mr2, g2, be2, None, G, want_sums=True)
         dvec = dout_sums if ctx.has_vec else None
-        dw2 = conv2d_wgrad(h1, None, ops.CONV_NORMAL, 3, dh2, Co, pro=(a1, c1))
-        dact1 = conv2d_dgrad(dh2, w2, 3, ops.CONV_NORMAL, Co)
+        opd = ctx.operands
+        dw2 = conv2d_wgrad(h1, None, ops.CONV_NORMAL, 3, dh2, Co, pro=(a1, c1), operands=opd)
+        dact1 = conv2d_dgrad(dh2, w2, 3, ops.CONV_NORMAL, Co, operands=opd)
         dh1, dg1, dbe1, dfilm, db1, _ = gn_silu_bwd(dact1, h1, a1, c1, mr1, g1, be1, film, G, want_sums=True)
-        dw1 = conv2d_wgrad(src0, src1, ops.CONV_NORMAL, 3, dh1, Cin)
+        dw1 = conv2d_wgrad(src0, src1, ops.CONV_NORMAL, 3, dh1, Cin, operands=opd)
         if wr is None:
             dres = dout  # identity residual (single source)
             dwr = dbr = None
         else:
-            dres = conv2d_dgrad(dout, wr, 1, ops.CONV_NORMAL, Cin)
-            dwr = conv2d_wgrad(src0, src1, ops.CONV_NORMAL, 1, dout, Cin)
+            dres = conv2d_dgrad(dout, wr, 1, ops.CONV_NORMAL, Cin, operands=opd)
+            dwr = conv2d_wgrad(src0, src1, ops.CONV_NORMAL, 1, dout, Cin, operands=opd)
             dbr = batch_sum(dout_sums)
-        dx = conv2d_dgrad(dh1, w1, 3, ops.CONV_NORMAL, Cin, res=dres)
+        dx = conv2d_dgrad(dh1, w1, 3, ops.CONV_NORMAL, Cin, res=dres, operands=opd)
         d0 = dx[:, :C0] if src1 is not None else dx
         d1 = dx[:, C0:] if src1 is not None else None
         return d0, d1, dfilm, dvec, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dwr, dbr, None, None, None
