@@ -451,6 +451,11 @@ int idiff_drift_reverse_step_dev(float* x, const float* r_hat, const float* e_ha
                                  uint64_t nper, uint64_t offset_base, idiff_stream_t stream);
 /* t <- t-1 (back to T once t <= t_stop), both counters += 1, tdev[0..B) = (float)t   (the UNets' timestep input) */
 int idiff_step_state_advance(int32_t* state, float* tdev, int B, int T, int t_stop, idiff_stream_t stream);
+/* Few-step schedule form (driftSDE sample_T / sample_timesteps): t <- next_t[t] (back to t_first once t <= t_stop), both counters += 1,
+ * tdev[0..B) = (float)t.  next_t int32[Tp1] maps each schedule point t_k to t_{k+1}; a t outside [0, Tp1) restarts at t_first, so
+ * next_t is never read out of bounds.  The coef rows of idiff_drift_reverse_step_dev are then the jump coefficients t_k -> t_{k+1}. */
+int idiff_step_state_advance_table(int32_t* state, float* tdev, int B, const int32_t* next_t, int Tp1, int t_first, int t_stop,
+                                   idiff_stream_t stream);
 /* Inverted dropout (training mode of the ScoreMapModule decoder blocks: nn.Dropout(0.1) in TransformerDecoderLayer / Attention.proj_drop,
  * models/_modified_BiomedCLIP.py:448-478,520-549): out[i] = x[i] / (1-p) where u_i >= p, else 0, with u_i = (w >> 8) * 2^-24 from word
  * i % 4 of Philox counter offset + i / 4 under `seed`.  The mask is a function of (seed, offset, i) alone: the backward pass is the SAME

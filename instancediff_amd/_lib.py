@@ -126,6 +126,7 @@ SIGNATURES = {
     "idiff_drift_reverse_step": (I, [P, P, P, P, P, P, P, I64, F, F, F, U64, U64, c_stream]),
     "idiff_drift_reverse_step_dev": (I, [P, P, P, P, P, P, I64, P, I, P, U64, U64, U64, c_stream]),
     "idiff_step_state_advance": (I, [P, P, I, I, I, c_stream]),
+    "idiff_step_state_advance_table": (I, [P, P, I, P, I, I, I, c_stream]),
     "idiff_randn": (I, [P, I64, U64, U64, c_stream]),
     "idiff_dropout": (I, [P, P, I64, F, U64, U64, c_stream]),
     "idiff_philox_raw": (I, [P, I64, U64, U64, c_stream]),

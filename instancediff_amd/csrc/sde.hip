@@ -171,6 +171,22 @@ __global__ void step_state_advance_kernel(int* state, float* tdev, int B, int T,
     }
 }
 
+// Few-step form: t <- next_t[t] along a host-built schedule t_0 > t_1 > ... > t_K = 0 (wrapping to t_first once t <= t_stop),
+// counters += 1, tdev[:] = t.  A t outside [0, Tp1), read or produced, restarts at t_first: next_t is never read out of bounds.
+__global__ void step_state_advance_table_kernel(int* state, float* tdev, int B, const int* __restrict__ next_t, int Tp1, int t_first,
+                                                int t_stop) {
+    const int cur = state[0];
+    int t = (cur >= 0 && cur < Tp1) ? next_t[cur] : t_first;
+    if (t <= t_stop || t >= Tp1) t = t_first;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) tdev[i] = (float)t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        state[0] = t;
+        state[1] += 1;
+        state[2] += 1;
+    }
+}
+
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, long long n, uint64_t seed, uint64_t offset) {
     const long long nv = (n + 3) / 4;
     for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x)
@@ -412,6 +428,15 @@ extern "C" int idiff_step_state_advance(int32_t* state, float* tdev, int B, int 
     IDIFF_CHECK_ARG(state && tdev && B > 0 && T > 0 && t_stop >= 0 && t_stop < T, "step_state_advance: bad args");
     hipLaunchKernelGGL(step_state_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, tdev, B, T, t_stop);
     IDIFF_CHECK_LAUNCH("step_state_advance");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_step_state_advance_table(int32_t* state, float* tdev, int B, const int32_t* next_t, int Tp1, int t_first, int t_stop,
+                                              idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(state && tdev && next_t && B > 0 && Tp1 > 1 && t_first > 0 && t_first < Tp1 && t_stop >= 0 && t_stop < t_first,
+                    "step_state_advance_table: bad args");
+    hipLaunchKernelGGL(step_state_advance_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, tdev, B, next_t, Tp1, t_first, t_stop);
+    IDIFF_CHECK_LAUNCH("step_state_advance_table");
     return IDIFF_OK;
 }
 

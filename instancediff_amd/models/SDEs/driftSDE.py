@@ -12,8 +12,13 @@ The reverse update is the build's frozen spec ("parity unpinned")
     x_{t-1} = x_t - a_t*R_hat - b_t*eps_hat + c_t*z,   R_hat = drift_net(x_t-cond, cond, t), eps_hat = noise_net(x_t-cond, x_t, t)
 with (a_t, b_t, c_t) from oracle-identical fp64 host arithmetic; ONE kernel per step does the update, draws z
 (Philox) and emits the next step's `x_t - cond` network input.
+
+Few-step sampling (`sample_T` / `sample_timesteps`): the same update evaluated as a jump between schedule points
+t_0 = T > t_1 > ... > t_K = 0 instead of t -> t-1.  The nets get t_k itself: the tables stay on the training grid, so unlike IRSDE's
+t*sample_scale no timestep rescaling is needed.  Training (forward_diffusion) is untouched and still draws t in [1, T].
 """
 import math
+import numbers
 import os
 
 import torch
@@ -55,9 +60,51 @@ def _step_coeffs(d, n, max_sigma, T, eta):
     return a.to(torch.float32), b.to(torch.float32), c.to(torch.float32)
 
 
+def _sample_schedule(T, sample_T=None, sample_timesteps=None):
+    """-> [t_0, ..., t_K = 0] for the reverse chain, or None when neither option is set (the plain T-step chain).
+    sample_T = K (1 <= K <= T): t_k = ((K - k) * T) // K, so t_0 = T, t_K = 0 and every gap is >= T // K.
+    sample_timesteps: a strictly decreasing list of ints in [1, T]; 0 is appended."""
+    def is_int(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if sample_T is not None and is_int(sample_T) and sample_T == -1:
+        sample_T = None
+    if sample_T is not None and sample_timesteps is not None:
+        raise ValueError("driftSDE: set sample_T or sample_timesteps, not both")
+    if sample_T is not None:
+        if not is_int(sample_T) or not 1 <= sample_T <= T:
+            raise ValueError(f"driftSDE: sample_T must be an int in [1, T={T}] (or -1 / None: unset), got {sample_T!r}")
+        K = int(sample_T)
+        return [((K - k) * T) // K for k in range(K + 1)]
+    if sample_timesteps is not None:
+        ts = list(sample_timesteps)
+        if not ts or not all(is_int(t) and 1 <= t <= T for t in ts) or any(a <= b for a, b in zip(ts, ts[1:])):
+            raise ValueError(f"driftSDE: sample_timesteps must be a non-empty, strictly decreasing list of ints in [1, T={T}], got {sample_timesteps!r}")
+        return [int(t) for t in ts] + [0]
+    return None
+
+
+def _jump_tables(d, n, max_sigma, T, eta, timesteps):
+    """Device tables of a schedule: coef [3, T+1] fp32 holds the jump t_k -> t_{k+1} in row t_k (k < K) and NaN in every other row;
+    next_t int32 [T+1] maps t_k to t_{k+1} and every other t to -1.  The expressions and their order are _step_coeffs' with t-1
+    replaced by s = t_{k+1}, in fp64, rounded once to fp32: the schedule T, T-1, ..., 0 gives its tables bit for bit."""
+    d = d.to(torch.float64)
+    sg = max_sigma * torch.sqrt(n.to(torch.float64))
+    coef = torch.full((3, T + 1), float("nan"), dtype=torch.float64)
+    next_t = torch.full((T + 1,), -1, dtype=torch.int32)
+    for t, s in zip(timesteps[:-1], timesteps[1:]):
+        ratio = (sg[s] / sg[t]) ** 2 if sg[t] > 0 else 0.0
+        et = eta * sg[s] * math.sqrt(max(1.0 - float(ratio), 0.0))
+        keep = math.sqrt(max(float(sg[s]) ** 2 - et ** 2, 0.0))
+        coef[0, t] = d[t] - d[s]
+        coef[1, t] = sg[t] - keep
+        coef[2, t] = et
+        next_t[t] = s
+    return coef.to(torch.float32), next_t
+
+
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
-                 **_ignored):
+                 sample_T=None, sample_timesteps=None, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -76,6 +123,28 @@ class driftSDE:
         self.two_streams = bool(int(os.environ.get("IDIFF_TWO_STREAMS", "1")))
         self.hip_graph = bool(int(os.environ.get("IDIFF_HIP_GRAPH", "1")))
         self._streams = None
+        self._jump = None  # ((timesteps, eta), coef, next_t) of the last schedule whose tables were built
+        self.set_sample_steps(sample_T, sample_timesteps)
+
+    def set_sample_steps(self, sample_T=None, sample_timesteps=None):
+        """Reverse-chain length: sample_T = K uniform jumps, or an explicit sample_timesteps list (0 appended); neither restores the
+        plain T-step chain.  Only reverse_ddpm reads it: the nets, the training sampler and the tables of the T-step chain stay."""
+        sched = _sample_schedule(self.T, sample_T, sample_timesteps)
+        self._sched = sched
+        if sched is not None:
+            self._schedule_tables(sched)
+
+    @property
+    def timesteps(self):
+        """the reverse chain's timesteps t_0 = T > ... > t_K = 0 (T, T-1, ..., 0 without a few-step schedule)"""
+        return list(self._sched) if self._sched is not None else list(range(self.T, -1, -1))
+
+    def _schedule_tables(self, timesteps):
+        """(coef [3, T+1] fp32, next_t int32 [T+1]) of a schedule, on the host; built once per schedule"""
+        key = (tuple(timesteps), self.eta)
+        if self._jump is None or self._jump[0] != key:
+            self._jump = (key,) + _jump_tables(self._h_drift, self._h_noise, self.max_sigma, self.T, self.eta, key[0])
+        return self._jump[1], self._jump[2]
 
     def set_gpu(self, device):
         self.device = device
@@ -154,17 +223,30 @@ class driftSDE:
         """The body of the reverse loop with every per-step scalar in device memory (timestep vector, (a_t, b_t, c_t) tables,
         Philox call count, step index), so the same launches serve every t -- eagerly, or as ONE captured HIP graph that is
         replayed per step (`IDIFF_HIP_GRAPH=0` disables the capture).  The graph holds the two UNet forwards on their two
-        streams, the fused update and the state advance; the host does not touch the loop between replays."""
+        streams, the fused update and the state advance; the host does not touch the loop between replays.
+        `timesteps` (a few-step schedule t_0 > ... > t_K = 0) swaps in the schedule's jump tables and the table-driven state advance;
+        without it the plain t -> t-1 chain runs."""
 
-        def __init__(self, sde, x, cond, names, text_encoder, image_context, noises=None, t_start=None, t_stop=0):
+        def __init__(self, sde, x, cond, names, text_encoder, image_context, noises=None, t_start=None, t_stop=0, timesteps=None):
             self.sde, self.names, self.text_encoder, self.ctx = sde, names, text_encoder, image_context
             dev = x.device
             self.x, self.cond = x, cond
             self.xa = ops.axpby(x, cond, 1.0, -1.0)
             self.T, self.t_stop = sde.T, int(t_stop)
-            t0 = sde.T if t_start is None else int(t_start)
-            self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
-            self.coef = torch.stack([sde._a, sde._b, sde._c]).to(device=dev, dtype=torch.float32).contiguous()
+            if timesteps is None:
+                self.next_t = None
+                t0 = sde.T if t_start is None else int(t_start)
+                self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
+                self.coef = torch.stack([sde._a, sde._b, sde._c]).to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                ts = list(timesteps)
+                if t_start is not None or len(ts) < 2 or ts[-1] != 0 or ts[0] > sde.T or any(a <= b for a, b in zip(ts, ts[1:])):
+                    raise ValueError(f"Stepper: timesteps must decrease strictly from at most T={sde.T} to 0 (no t_start), got {ts}")
+                t0 = self.t_first = ts[0]
+                self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
+                coef, next_t = sde._schedule_tables(ts)
+                self.coef = coef.to(dev).contiguous()
+                self.next_t = next_t.to(dev).contiguous()
             self.state = torch.tensor([t0, 0, 0], dtype=torch.int32, device=dev)  # {t, draws of this run, step index}
             self.noises = None if noises is None else noises.contiguous()
             self.nper = (x.numel() + 3) // 4
@@ -176,7 +258,10 @@ class driftSDE:
             sde = self.sde
             r_hat, e_hat = sde.predict(self.xa, self.x, self.cond, self.tdev, self.names, self.text_encoder, self.ctx)
             ops.drift_reverse_step_dev(self.x, r_hat, e_hat, self.noises, self.cond, self.xa, self.coef, self.state, sde.seed, self.nper, self.off_base)
-            ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
+            if self.next_t is None:
+                ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
+            else:
+                ops.step_state_advance_table(self.state, self.tdev, self.next_t, self.t_first, self.t_stop)
 
         def _warm_step(self):
             """one step eagerly on the side stream: fills every weight / text cache outside the graph's memory pool.  It IS a
@@ -248,7 +333,9 @@ class driftSDE:
     def reverse_ddpm(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None, x_T=None,
                      noises=None, T_stop=0):
         """Iterative denoising from x_T = cond + max_sigma*z down to t=1.  `noises` (optional, [T, ...]) injects
-        the per-step draws (parity runs; noises[i] is used at loop iteration i, t = T-i); x_T optional."""
+        the per-step draws (parity runs; noises[i] is used at loop iteration i, t = T-i); x_T optional.
+        With a few-step schedule (sample_T / sample_timesteps) the loop runs K = len(timesteps) - 1 jumps t_k -> t_{k+1}, noises is
+        [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran."""
         if optimize_type not in ("inputRes", "predict_noise", ""):
             raise NotImplementedError(f"optimize_type={optimize_type!r}: only the active 'inputRes' path of the reference "
                                       "(drift_noise_model.py:231-232) is in scope")
@@ -256,12 +343,24 @@ class driftSDE:
             # optimize_target (drift_noise_model.py:68,581-604): 'std*' nets predict LQ-GT and the standard noise, which is what
             # the update consumes; 'scaled*' nets predict d_t*(LQ-GT) and s_t*eps and would need rescaling -- not silently ignored
             raise NotImplementedError(f"reverse_type={reverse_type!r}: only the 'std' prediction targets of config.yml:144 are in scope")
+        sched = self._sched
+        if sched is not None:
+            if T_stop not in sched:
+                raise ValueError(f"reverse_ddpm: T_stop={T_stop} is not a point of the schedule {sched}")
+            nsteps = sched.index(T_stop)
+            if noises is not None and noises.shape[0] < nsteps:
+                raise ValueError(f"reverse_ddpm: noises holds {noises.shape[0]} draws for a {nsteps}-step chain")
         cond = cond.contiguous()
         B = cond.shape[0]
         if x_T is None:
             x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
         x = x_T.contiguous().clone()
-        stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
-        out = stepper.run(self.T - T_stop)
+        if sched is None:
+            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
+            nsteps = self.T - T_stop
+        else:
+            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched)
+        out = stepper.run(nsteps)
         self.last_mode = stepper.mode  # 'graph' | 'eager': how the loop of this call ran
+        self.last_steps = nsteps
         return out

@@ -795,6 +795,15 @@ def step_state_advance(state, tdev, T, t_stop=0):
     check(lib.idiff_step_state_advance(C.c_void_p(state.data_ptr()), _p(tdev), tdev.numel(), T, t_stop, _stream()), "step_state_advance")
 
 
+def step_state_advance_table(state, tdev, next_t, t_first, t_stop=0):
+    """few-step form: t <- next_t[t] (int32 [T+1] on the device), back to t_first once t <= t_stop"""
+    lib = _lib.load()
+    _c(tdev, "tdev"), _c(state, "state", torch.int32), _c(next_t, "next_t", torch.int32)
+    assert state.numel() == 3 and next_t.dim() == 1
+    check(lib.idiff_step_state_advance_table(C.c_void_p(state.data_ptr()), _p(tdev), tdev.numel(), C.c_void_p(next_t.data_ptr()),
+                                             next_t.numel(), t_first, t_stop, _stream()), "step_state_advance_table")
+
+
 def randn(shape, device, seed, offset=0):
     lib = _lib.load()
     out = torch.empty(shape, device=device, dtype=torch.float32)

@@ -27,6 +27,8 @@ def main(argv=None):
     parser.add_argument("-opt", type=str, required=True, help="Path to options YAML file.")
     parser.add_argument("--random-init", action="store_true", help="skip model.load (no checkpoint; synthetic smoke run)")
     parser.add_argument("--limit", type=int, default=0, help="stop after N images")
+    parser.add_argument("--sample-T", type=int, default=None, metavar="K",
+                        help="reverse-chain steps per image (driftSDE sample_T: K uniform jumps over the T-step schedule)")
     args = parser.parse_args(argv)
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
@@ -38,7 +40,11 @@ def main(argv=None):
     model = create_model(train_opt, opt['models'][test_opt['which_model']], phase='test')
     if not args.random_init:
         model.load(test_opt['iter'], test_opt['pth_dir'])
-    sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), opt['sdes'][test_opt['which_sde']])
+    sde_opt = dict(opt['sdes'][test_opt['which_sde']])
+    if args.sample_T is not None:
+        sde_opt.pop('sample_timesteps', None)
+        sde_opt['sample_T'] = args.sample_T
+    sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
     model.set_eval()
@@ -80,7 +86,7 @@ def main(argv=None):
         if v['num']:
             print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR')))
     if times:
-        print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({sde.T} steps)")
+        print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)")
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return results
