@@ -449,6 +449,21 @@ int idiff_drift_reverse_step(const float* x, const float* r_hat, const float* e_
 int idiff_drift_reverse_step_dev(float* x, const float* r_hat, const float* e_hat, const float* z_base, const float* cond,
                                  float* xa, int64_t n, const float* coef, int Tp1, const int32_t* state, uint64_t seed,
                                  uint64_t nper, uint64_t offset_base, idiff_stream_t stream);
+/* Second-order multistep form of idiff_drift_reverse_step_dev (driftSDE solver_order = 2): each prediction is
+ * extrapolated linearly from the previous jump's before the same update, at no extra network evaluation.
+ *   coef5 float[5][Tp1] = tables of (a, b, c, rho_d, rho_s), read at t = state[0];  state, seed, nper, offset_base and z_base are those
+ *   of idiff_drift_reverse_step_dev: for the same (seed, offset_base, state) the two entry points draw the same z.
+ *   r_prev, e_prev [n]: the previous jump's r_hat / e_hat, kept by this call at fixed addresses for the next replay.  They must be
+ *   distinct from each other and from every other operand.
+ * fp32 operation order, one rounding per operation, no contraction:
+ *   R~ = r_hat + rho_d*(r_hat - r_prev)        (R~ = r_hat and r_prev is not read when rho_d == 0)
+ *   e~ = e_hat + rho_s*(e_hat - e_prev)        (e~ = e_hat and e_prev is not read when rho_s == 0)
+ *   x  <- ((x - a*R~) - b*e~) + c*z ;   xa <- x - cond ;   r_prev <- r_hat ;   e_prev <- e_hat        (all in place)
+ * With rho_d == rho_s == 0 (the first jump of a chain) the result is bit-identical to idiff_drift_reverse_step_dev with the same a, b, c
+ * whatever the history holds, uninitialised memory and NaNs included.  A NaN rho (a row that starts no jump) counts as non-zero. */
+int idiff_drift_reverse_step2_dev(float* x, const float* r_hat, const float* e_hat, float* r_prev, float* e_prev, const float* z_base,
+                                  const float* cond, float* xa, int64_t n, const float* coef5, int Tp1, const int32_t* state,
+                                  uint64_t seed, uint64_t nper, uint64_t offset_base, idiff_stream_t stream);
 /* t <- t-1 (back to T once t <= t_stop), both counters += 1, tdev[0..B) = (float)t   (the UNets' timestep input) */
 int idiff_step_state_advance(int32_t* state, float* tdev, int B, int T, int t_stop, idiff_stream_t stream);
 /* Few-step schedule form (driftSDE sample_T / sample_timesteps): t <- next_t[t] (back to t_first once t <= t_stop), both counters += 1,

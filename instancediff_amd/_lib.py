@@ -125,6 +125,7 @@ SIGNATURES = {
     "idiff_irsde_map": (I, [I, P, P, P, P, F, P, I, I64, P, C.POINTER(C.c_float), U64, U64, c_stream]),
     "idiff_drift_reverse_step": (I, [P, P, P, P, P, P, P, I64, F, F, F, U64, U64, c_stream]),
     "idiff_drift_reverse_step_dev": (I, [P, P, P, P, P, P, I64, P, I, P, U64, U64, U64, c_stream]),
+    "idiff_drift_reverse_step2_dev": (I, [P, P, P, P, P, P, P, P, I64, P, I, P, U64, U64, U64, c_stream]),
     "idiff_step_state_advance": (I, [P, P, I, I, I, c_stream]),
     "idiff_step_state_advance_table": (I, [P, P, I, P, I, I, I, c_stream]),
     "idiff_randn": (I, [P, I64, U64, U64, c_stream]),

@@ -157,6 +157,57 @@ __global__ __launch_bounds__(256) void drift_step_dev_kernel(float* x, const flo
     }
 }
 
+// Second-order multistep form of drift_step_dev_kernel (driftSDE solver_order = 2): coef = [5][Tp1] tables of (a, b, c, rho_d, rho_s);
+// each prediction is extrapolated linearly from the previous jump's, kept in rp / ep at fixed addresses for the next replay:
+//   R~ = r + rho_d*(r - rp),  e~ = e + rho_s*(e - ep),  x <- ((x - a*R~) - b*e~) + c*z,  xa <- x - cond,  rp <- r,  ep <- e.
+// rho_d, rho_s are uniform over the grid.  A zero rho skips that clock's history read and its term (the first jump of a chain, a
+// flat level table), so with both zero the arithmetic is drift_step_dev_kernel's whatever rp / ep hold.  Element-wise and in place:
+// each thread reads its own elements before it writes them.
+__global__ __launch_bounds__(256) void drift_step2_dev_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh, float* rp,
+                                                              float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
+                                                              float* xa, long long n, const float* __restrict__ coef, int Tp1,
+                                                              const int* __restrict__ state, uint64_t seed, uint64_t nper,
+                                                              uint64_t offset_base) {
+    const int t = state[0];
+    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
+    const float rho_d = coef[3 * Tp1 + t], rho_s = coef[4 * Tp1 + t];
+    const bool hist_d = rho_d != 0.f, hist_s = rho_s != 0.f;  // true for NaN too: an off-schedule row poisons the result
+    const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
+    const float* z = zbase ? zbase + (long long)state[2] * n : nullptr;
+    const long long nv = (n + 3) / 4;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
+        const long long i = v * 4;
+        const floatx4 xv = ld4(x, i, n), rv = ld4(rh, i, n), ev = ld4(eh, i, n);
+        floatx4 rt = rv, et = ev;
+        if (hist_d) {
+            const floatx4 pv = ld4(rp, i, n);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
+        }
+        if (hist_s) {
+            const floatx4 pv = ld4(ep, i, n);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
+        }
+        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
+        if (c != 0.f) zv = z ? ld4(z, i, n) : philox_normal4(offset + (uint64_t)v, seed);
+        const floatx4 cv = ld4(cond, i, n);
+        floatx4 o, oa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
+            r = __fsub_rn(r, __fmul_rn(b, et[k]));
+            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
+            o[k] = r;
+            oa[k] = __fsub_rn(r, cv[k]);
+        }
+        st4(x, i, n, o);
+        st4(xa, i, n, oa);
+        st4(rp, i, n, rv);
+        st4(ep, i, n, ev);
+    }
+}
+
 // t <- t-1 (wrapping to T below t_stop+1, for benchmark loops), counters += 1, tdev[:] = t  -- the host never touches a
 // per-step scalar between graph replays
 __global__ void step_state_advance_kernel(int* state, float* tdev, int B, int T, int t_stop) {
@@ -421,6 +472,20 @@ extern "C" int idiff_drift_reverse_step_dev(float* x, const float* r_hat, const 
     hipLaunchKernelGGL(drift_step_dev_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, z_base, cond, xa,
                        (long long)n, coef, Tp1, state, seed, nper, offset_base);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_dev");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_drift_reverse_step2_dev(float* x, const float* r_hat, const float* e_hat, float* r_prev, float* e_prev, const float* z_base,
+                                             const float* cond, float* xa, int64_t n, const float* coef5, int Tp1, const int32_t* state,
+                                             uint64_t seed, uint64_t nper, uint64_t offset_base, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(x && r_hat && e_hat && r_prev && e_prev && cond && xa && coef5 && state && n > 0 && Tp1 > 1,
+                    "drift_reverse_step2_dev: bad args");
+    IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_hat && r_prev != e_hat && e_prev != r_hat && e_prev != e_hat && r_prev != x && e_prev != x &&
+                        r_prev != xa && e_prev != xa,
+                    "drift_reverse_step2_dev: the history buffers must be distinct from each other and from every other operand");
+    hipLaunchKernelGGL(drift_step2_dev_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev,
+                       z_base, cond, xa, (long long)n, coef5, Tp1, state, seed, nper, offset_base);
+    IDIFF_CHECK_LAUNCH("drift_reverse_step2_dev");
     return IDIFF_OK;
 }
 

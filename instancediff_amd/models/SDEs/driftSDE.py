@@ -16,6 +16,10 @@ with (a_t, b_t, c_t) from oracle-identical fp64 host arithmetic; ONE kernel per 
 Few-step sampling (`sample_T` / `sample_timesteps`): the same update evaluated as a jump between schedule points
 t_0 = T > t_1 > ... > t_K = 0 instead of t -> t-1.  The nets get t_k itself: the tables stay on the training grid, so unlike IRSDE's
 t*sample_scale no timestep rescaling is needed.  Training (forward_diffusion) is untouched and still draws t in [1, T].
+
+Second-order multistep solver (`solver_order: 2`): the deterministic reverse path is the quadrature dx = R_hat dd + eps_hat dsigma,
+so each jump extrapolates the two predictions linearly from the previous jump's, each in its own clock (two-step Adams-Bashforth with
+variable steps), at no extra network evaluation.  It always runs the schedule path; order 1 (the default) is the update above, unchanged.
 """
 import math
 import numbers
@@ -83,13 +87,26 @@ def _sample_schedule(T, sample_T=None, sample_timesteps=None):
     return None
 
 
-def _jump_tables(d, n, max_sigma, T, eta, timesteps):
+def _solver_order(order):
+    """1 (None: unset) or 2, as an int; anything else -- bools, floats and strings included -- is refused"""
+    if order is None:
+        return 1
+    if not isinstance(order, numbers.Integral) or isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"driftSDE: solver_order must be the int 1 or 2, got {order!r}")
+    return int(order)
+
+
+def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
     """Device tables of a schedule: coef [3, T+1] fp32 holds the jump t_k -> t_{k+1} in row t_k (k < K) and NaN in every other row;
     next_t int32 [T+1] maps t_k to t_{k+1} and every other t to -1.  The expressions and their order are _step_coeffs' with t-1
-    replaced by s = t_{k+1}, in fp64, rounded once to fp32: the schedule T, T-1, ..., 0 gives its tables bit for bit."""
+    replaced by s = t_{k+1}, in fp64, rounded once to fp32: the schedule T, T-1, ..., 0 gives its tables bit for bit.
+    order = 2: coef is [5, T+1]; rows 0-2 are the order-1 rows, rows 3-4 the extrapolation weights of the two clocks with p = t_{k-1}:
+        rho_d = (0.5 * (d_t - d_s)) / (d_p - d_t)        rho_s = (0.5 * (sg_t - sg_s)) / (sg_p - sg_t)
+    in fp64 in that order, rounded once; both 0 in row t_0 (no history), and a clock whose denominator is exactly 0 gets 0 for that
+    jump (that clock alone falls back to first order)."""
     d = d.to(torch.float64)
     sg = max_sigma * torch.sqrt(n.to(torch.float64))
-    coef = torch.full((3, T + 1), float("nan"), dtype=torch.float64)
+    coef = torch.full((3 if order == 1 else 5, T + 1), float("nan"), dtype=torch.float64)
     next_t = torch.full((T + 1,), -1, dtype=torch.int32)
     for t, s in zip(timesteps[:-1], timesteps[1:]):
         ratio = (sg[s] / sg[t]) ** 2 if sg[t] > 0 else 0.0
@@ -99,12 +116,18 @@ def _jump_tables(d, n, max_sigma, T, eta, timesteps):
         coef[1, t] = sg[t] - keep
         coef[2, t] = et
         next_t[t] = s
+    if order == 2:
+        coef[3:, timesteps[0]] = 0.0
+        for p, t, s in zip(timesteps[:-2], timesteps[1:-1], timesteps[2:]):
+            for row, lv in ((3, d), (4, sg)):
+                den = lv[p] - lv[t]
+                coef[row, t] = (0.5 * (lv[t] - lv[s])) / den if float(den) != 0.0 else 0.0
     return coef.to(torch.float32), next_t
 
 
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
-                 sample_T=None, sample_timesteps=None, **_ignored):
+                 sample_T=None, sample_timesteps=None, solver_order=None, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -123,8 +146,13 @@ class driftSDE:
         self.two_streams = bool(int(os.environ.get("IDIFF_TWO_STREAMS", "1")))
         self.hip_graph = bool(int(os.environ.get("IDIFF_HIP_GRAPH", "1")))
         self._streams = None
-        self._jump = None  # ((timesteps, eta), coef, next_t) of the last schedule whose tables were built
+        self._jump = None  # ((timesteps, eta, order), coef, next_t) of the last schedule whose tables were built
+        self.solver_order = _solver_order(solver_order)
         self.set_sample_steps(sample_T, sample_timesteps)
+
+    def set_solver_order(self, order=None):
+        """1 (or None): the first-order jump; 2: the second-order multistep jump (reverse_ddpm only, like set_sample_steps)"""
+        self.solver_order = _solver_order(order)
 
     def set_sample_steps(self, sample_T=None, sample_timesteps=None):
         """Reverse-chain length: sample_T = K uniform jumps, or an explicit sample_timesteps list (0 appended); neither restores the
@@ -139,11 +167,13 @@ class driftSDE:
         """the reverse chain's timesteps t_0 = T > ... > t_K = 0 (T, T-1, ..., 0 without a few-step schedule)"""
         return list(self._sched) if self._sched is not None else list(range(self.T, -1, -1))
 
-    def _schedule_tables(self, timesteps):
-        """(coef [3, T+1] fp32, next_t int32 [T+1]) of a schedule, on the host; built once per schedule"""
-        key = (tuple(timesteps), self.eta)
+    def _schedule_tables(self, timesteps, order=None):
+        """(coef [3, T+1] fp32 -- [5, T+1] for solver order 2 --, next_t int32 [T+1]) of a schedule, on the host; built once per
+        schedule and order (order None: the sde's own)"""
+        order = self.solver_order if order is None else _solver_order(order)
+        key = (tuple(timesteps), self.eta, order)
         if self._jump is None or self._jump[0] != key:
-            self._jump = (key,) + _jump_tables(self._h_drift, self._h_noise, self.max_sigma, self.T, self.eta, key[0])
+            self._jump = (key,) + _jump_tables(self._h_drift, self._h_noise, self.max_sigma, self.T, self.eta, key[0], order)
         return self._jump[1], self._jump[2]
 
     def set_gpu(self, device):
@@ -225,14 +255,19 @@ class driftSDE:
         replayed per step (`IDIFF_HIP_GRAPH=0` disables the capture).  The graph holds the two UNet forwards on their two
         streams, the fused update and the state advance; the host does not touch the loop between replays.
         `timesteps` (a few-step schedule t_0 > ... > t_K = 0) swaps in the schedule's jump tables and the table-driven state advance;
-        without it the plain t -> t-1 chain runs."""
+        without it the plain t -> t-1 chain runs.  `solver_order` = 2 (needs `timesteps`) swaps in the second-order update, its
+        5-row table and the two history buffers it keeps between replays."""
 
-        def __init__(self, sde, x, cond, names, text_encoder, image_context, noises=None, t_start=None, t_stop=0, timesteps=None):
+        def __init__(self, sde, x, cond, names, text_encoder, image_context, noises=None, t_start=None, t_stop=0, timesteps=None,
+                     solver_order=1):
             self.sde, self.names, self.text_encoder, self.ctx = sde, names, text_encoder, image_context
             dev = x.device
             self.x, self.cond = x, cond
             self.xa = ops.axpby(x, cond, 1.0, -1.0)
             self.T, self.t_stop = sde.T, int(t_stop)
+            self.order = _solver_order(solver_order)
+            if self.order == 2 and timesteps is None:
+                raise ValueError("Stepper: solver_order = 2 runs on a schedule (timesteps)")
             if timesteps is None:
                 self.next_t = None
                 t0 = sde.T if t_start is None else int(t_start)
@@ -244,7 +279,7 @@ class driftSDE:
                     raise ValueError(f"Stepper: timesteps must decrease strictly from at most T={sde.T} to 0 (no t_start), got {ts}")
                 t0 = self.t_first = ts[0]
                 self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
-                coef, next_t = sde._schedule_tables(ts)
+                coef, next_t = sde._schedule_tables(ts, self.order)
                 self.coef = coef.to(dev).contiguous()
                 self.next_t = next_t.to(dev).contiguous()
             self.state = torch.tensor([t0, 0, 0], dtype=torch.int32, device=dev)  # {t, draws of this run, step index}
@@ -253,11 +288,17 @@ class driftSDE:
             self.off_base = sde._off  # this run's draws start where the stream's earlier ones ended
             self.graph = None
             self.steps_done = 0
+            if self.order == 2:  # the previous jump's predictions; not read at t_0, whose rho rows are 0
+                self.r_prev, self.e_prev = torch.empty_like(x), torch.empty_like(x)
 
         def _body(self):
             sde = self.sde
             r_hat, e_hat = sde.predict(self.xa, self.x, self.cond, self.tdev, self.names, self.text_encoder, self.ctx)
-            ops.drift_reverse_step_dev(self.x, r_hat, e_hat, self.noises, self.cond, self.xa, self.coef, self.state, sde.seed, self.nper, self.off_base)
+            if self.order == 2:
+                ops.drift_reverse_step2_dev(self.x, r_hat, e_hat, self.r_prev, self.e_prev, self.noises, self.cond, self.xa, self.coef, self.state,
+                                            sde.seed, self.nper, self.off_base)
+            else:
+                ops.drift_reverse_step_dev(self.x, r_hat, e_hat, self.noises, self.cond, self.xa, self.coef, self.state, sde.seed, self.nper, self.off_base)
             if self.next_t is None:
                 ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
             else:
@@ -335,7 +376,8 @@ class driftSDE:
         """Iterative denoising from x_T = cond + max_sigma*z down to t=1.  `noises` (optional, [T, ...]) injects
         the per-step draws (parity runs; noises[i] is used at loop iteration i, t = T-i); x_T optional.
         With a few-step schedule (sample_T / sample_timesteps) the loop runs K = len(timesteps) - 1 jumps t_k -> t_{k+1}, noises is
-        [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran."""
+        [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran.
+        solver_order = 2 always runs the schedule path (T, T-1, ..., 0 when no schedule is set).  self.last_solver_order: the order that ran."""
         if optimize_type not in ("inputRes", "predict_noise", ""):
             raise NotImplementedError(f"optimize_type={optimize_type!r}: only the active 'inputRes' path of the reference "
                                       "(drift_noise_model.py:231-232) is in scope")
@@ -343,7 +385,8 @@ class driftSDE:
             # optimize_target (drift_noise_model.py:68,581-604): 'std*' nets predict LQ-GT and the standard noise, which is what
             # the update consumes; 'scaled*' nets predict d_t*(LQ-GT) and s_t*eps and would need rescaling -- not silently ignored
             raise NotImplementedError(f"reverse_type={reverse_type!r}: only the 'std' prediction targets of config.yml:144 are in scope")
-        sched = self._sched
+        order = self.solver_order
+        sched = self._sched if (self._sched is not None or order == 1) else self.timesteps
         if sched is not None:
             if T_stop not in sched:
                 raise ValueError(f"reverse_ddpm: T_stop={T_stop} is not a point of the schedule {sched}")
@@ -359,8 +402,10 @@ class driftSDE:
             stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
             nsteps = self.T - T_stop
         else:
-            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched)
+            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched,
+                                       solver_order=order)
         out = stepper.run(nsteps)
         self.last_mode = stepper.mode  # 'graph' | 'eager': how the loop of this call ran
         self.last_steps = nsteps
+        self.last_solver_order = order
         return out

@@ -789,6 +789,19 @@ def drift_reverse_step_dev(x, r_hat, e_hat, z_base, cond, xa, coef, state, seed,
                                            C.c_void_p(state.data_ptr()), seed, nper, offset_base, _stream()), "drift_reverse_step_dev")
 
 
+def drift_reverse_step2_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, coef5, state, seed, nper, offset_base=0):
+    """second-order multistep form of drift_reverse_step_dev: `coef5` [5, T+1] adds the rows (rho_d, rho_s); r_prev / e_prev hold the
+    previous jump's predictions and are overwritten with this jump's (not read where rho == 0)"""
+    lib = _lib.load()
+    _c(x, "x"), _c(r_hat, "r_hat"), _c(e_hat, "e_hat"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
+    _c(xa, "xa"), _c(coef5, "coef5")
+    assert state.dtype == torch.int32 and state.is_cuda and state.numel() == 3 and coef5.dim() == 2 and coef5.shape[0] == 5
+    assert r_prev.numel() == x.numel() and e_prev.numel() == x.numel()
+    check(lib.idiff_drift_reverse_step2_dev(_p(x), _p(r_hat), _p(e_hat), _p(r_prev), _p(e_prev), _p(z_base), _p(cond), _p(xa), x.numel(),
+                                            _p(coef5), coef5.shape[1], C.c_void_p(state.data_ptr()), seed, nper, offset_base, _stream()),
+          "drift_reverse_step2_dev")
+
+
 def step_state_advance(state, tdev, T, t_stop=0):
     lib = _lib.load()
     _c(tdev, "tdev")

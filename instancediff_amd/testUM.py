@@ -29,6 +29,8 @@ def main(argv=None):
     parser.add_argument("--limit", type=int, default=0, help="stop after N images")
     parser.add_argument("--sample-T", type=int, default=None, metavar="K",
                         help="reverse-chain steps per image (driftSDE sample_T: K uniform jumps over the T-step schedule)")
+    parser.add_argument("--solver-order", type=int, default=None, metavar="N", choices=(1, 2),
+                        help="driftSDE solver_order: 1 = first-order jumps, 2 = second-order multistep jumps (overrides the YAML)")
     args = parser.parse_args(argv)
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
@@ -44,6 +46,8 @@ def main(argv=None):
     if args.sample_T is not None:
         sde_opt.pop('sample_timesteps', None)
         sde_opt['sample_T'] = args.sample_T
+    if args.solver_order is not None:
+        sde_opt['solver_order'] = args.solver_order
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
@@ -86,7 +90,8 @@ def main(argv=None):
         if v['num']:
             print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR')))
     if times:
-        print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)")
+        print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
+              + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else ""))
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return results
