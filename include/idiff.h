@@ -195,7 +195,10 @@ int idiff_linear_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, c
                      int64_t ldr, const float* gscale, float* out, int64_t ldo, int R, int K, int N, int act_in,
                      int act_out, idiff_stream_t stream);
 /* same contract with a PRE-TRANSPOSED weight wT [K, N] (row stride ldw): lane = output feature, unit-stride weight
- * reads, no cross-lane reduction -- the low-latency form used for the ScoreMapModule token chain. */
+ * reads, no cross-lane reduction -- the low-latency form used for the ScoreMapModule token chain.
+ * The rows of x are staged in LDS: K <= 2044 on the matrix-core kernel (N % 4 == 0, ldw % 4 == 0, wT 16-byte aligned), K <= 4864 on the
+ * vector kernel that takes every other shape (160 KiB of LDS per workgroup); a larger K returns IDIFF_E_UNSUPPORTED (IDIFF_E_BADARG
+ * beyond 8192). */
 int idiff_linear_t_fwd(const float* x, int64_t ldx, const float* wT, int64_t ldw, const float* bias, const float* res,
                        int64_t ldr, const float* gscale, float* out, int64_t ldo, int R, int K, int N, int act_in,
                        int act_out, idiff_stream_t stream);
@@ -295,7 +298,8 @@ int idiff_chan_layernorm_fwd(const float* x, int64_t x_bstride, const float* gam
  * Attention.  All follow _modified_BiomedCLIP.py:464-478:  softmax(q k^T * scale) v  per head.
  * ---------------------------------------------------------------------------------------------- */
 /* self-attention over a feature map: qkv [B, 3C, N] channel-major (q rows 0..C-1, k C..2C-1, v 2C..3C-1),
- * out [B, C, N]; head h owns channels h*dh..(h+1)*dh-1; dh must be 64 or 32; flash-style on f32 MFMA.
+ * out [B, C, N]; head h owns channels h*dh..(h+1)*dh-1; dh must be 64 or 32 and N a multiple of 4 (16-byte key loads);
+ * flash-style on f32 MFMA.
  * lse (optional) [B, heads, N] = log-sum-exp per query for the backward pass. */
 int idiff_attn_self_fwd(const float* qkv, float* out, float* lse, int B, int C, int N, int heads, float scale,
                         idiff_stream_t stream);
@@ -309,7 +313,8 @@ int idiff_attn_self_f16_fwd(const float* qkv, float* out, int B, int C, int N, i
 int idiff_attn_ctx_fwd(const float* q, const float* k, const float* v, float* out, int B, int C, int N, int M,
                        int heads, float scale, idiff_stream_t stream);
 /* tiny token-major attention (ScoreMapModule decoder self-attention): q [B,Nq,C] (row stride ldq), k,v [B,M,C]
- * (row stride ldkv) -- strides let q/k/v be slices of one packed qkv projection; out [B,Nq,C] dense; Nq,M <= 64 */
+ * (row stride ldkv) -- strides let q/k/v be slices of one packed qkv projection; out [B,Nq,C] dense; M <= 64 (a lane per key);
+ * Nq is not limited (a wave per query); any head dim C / heads */
 int idiff_attn_tokens_fwd(const float* q, const float* k, const float* v, float* out, int B, int Nq, int M, int C,
                           int heads, float scale, int64_t ldq, int64_t ldkv, idiff_stream_t stream);
 /* Backward of idiff_attn_tokens_fwd for few tokens (Nq, M <= 8; head dim <= 64) -- the class-token self-attention of the ScoreMapModule

@@ -846,6 +846,8 @@ static int linear_t_launch(const float* x, int64_t ldx, const float* wT, int64_t
     }
     dim3 grid((N + 63) / 64, (R + LT_ROWS - 1) / LT_ROWS, heads);
     const size_t lds = ((size_t)LT_ROWS * K + 4 * LT_ROWS * 64) * sizeof(float);
+    // the kernel stages LT_ROWS rows of K floats: beyond K = 4864 that is more than the 160 KiB of LDS a workgroup can have
+    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "linear_t_fwd: K = %d needs %zu bytes of LDS (K <= 4864)", K, lds);
     static size_t attr = 0;
     if (lds > 64 * 1024 && lds > attr) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_t_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
