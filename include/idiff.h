@@ -397,7 +397,9 @@ int idiff_conv3x3_select_fwd(const float* x, int64_t x_bstride, const float* w, 
                              int B, int C, int K, int H, int W, idiff_stream_t stream);
 /* Its backward (training step): dx [B,C,H,W] (dx_bstride) = the transposed conv of dpred [B,1,H,W] with each sample's class kernel,
  * dw [K,C,3,3] / db [K] (db may be NULL) = sums over the samples of each class (classes without a sample get zeros); either of dx / dw
- * may be NULL.  W % 4 == 0.  ws: idiff_conv3x3_select_bwd_ws_floats(B, C, H, W) floats (per-tile partials, reduced in a fixed order). */
+ * may be NULL.  W % 4 == 0.  ws: idiff_conv3x3_select_bwd_ws_floats(B, C, H, W) floats (per-tile partials, reduced in a fixed order).
+ * Every argument is checked before the first launch: a call that returns IDIFF_E_BADARG (a missing ws with dw set included) has
+ * written nothing, dx included. */
 int64_t idiff_conv3x3_select_bwd_ws_floats(int B, int C, int H, int W);
 int idiff_conv3x3_select_bwd(const float* x, int64_t x_bstride, const float* w, const int32_t* idx, const float* dpred, float* dx,
                              int64_t dx_bstride, float* dw, float* db, float* ws, int B, int C, int K, int H, int W, idiff_stream_t stream);

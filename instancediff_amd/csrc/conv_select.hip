@@ -258,16 +258,17 @@ extern "C" int idiff_conv3x3_select_bwd(const float* x, int64_t x_bstride, const
     IDIFF_CHECK_ARG(x && w && idx && dpred && (dx || dw), "conv3x3_select_bwd: null pointer");
     IDIFF_CHECK_ARG(B > 0 && C > 0 && C <= 256 && K > 0 && H > 0 && W > 0 && W % 4 == 0, "conv3x3_select_bwd: bad dims (W %% 4 == 0, C <= 256)");
     IDIFF_CHECK_ARG(x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "conv3x3_select_bwd: x must have 16-byte rows");
+    // every argument check comes before the first launch: a refused call writes nothing
+    IDIFF_CHECK_ARG(!dx || (dx_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0), "conv3x3_select_bwd: dx must have 16-byte rows");
+    IDIFF_CHECK_ARG(!dw || ws, "conv3x3_select_bwd: the weight gradient needs a workspace of idiff_conv3x3_select_bwd_ws_floats() floats");
     hipStream_t st = (hipStream_t)stream;
     const long long HW = (long long)H * W;
     if (dx) {
-        IDIFF_CHECK_ARG(dx_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0, "conv3x3_select_bwd: dx must have 16-byte rows");
         hipLaunchKernelGGL(conv3x3_select_dgrad_kernel, dim3((unsigned)((HW / 4 + 255) / 256), B), dim3(256), (size_t)C * 9 * sizeof(float), st, dpred, w, idx, dx,
                            (long long)dx_bstride, C, H, W);
         IDIFF_CHECK_LAUNCH("conv3x3_select_dgrad");
     }
     if (dw) {
-        IDIFF_CHECK_ARG(ws, "conv3x3_select_bwd: the weight gradient needs a workspace of idiff_conv3x3_select_bwd_ws_floats() floats");
         const int ntile = select_bwd_tiles(H, W);
         hipLaunchKernelGGL(conv3x3_select_wgrad_kernel, dim3(ntile, B), dim3(256), (size_t)(C * 36 + 4) * sizeof(float), st, x, (long long)x_bstride, dpred, ws, C,
                            H, W, ntile);
