@@ -471,6 +471,32 @@ int idiff_drift_reverse_step_dev(float* x, const float* r_hat, const float* e_ha
 int idiff_drift_reverse_step2_dev(float* x, const float* r_hat, const float* e_hat, float* r_prev, float* e_prev, const float* z_base,
                                   const float* cond, float* xa, int64_t n, const float* coef5, int Tp1, const int32_t* state,
                                   uint64_t seed, uint64_t nper, uint64_t offset_base, idiff_stream_t stream);
+/* ---- posterior ensembles: member noise streams ----
+ * Philox4x32-10 takes a 128-bit counter; every entry point above uses 64 bits of it (words c2 = c3 = 0).  A member stream uses the rest:
+ *   counter words (c0, c1, c2, c3) = (lo32(q), hi32(q), lo32(m), hi32(m)),  key = seed,  word -> normal mapping as in idiff_randn;
+ *   m = member id >= 1 (m = 0 is the stream of the entry points above; the host wrappers refuse it, so no member stream overlaps it);
+ *   q = j*Q + v,  Q = n_s/4,  n_s = elements of ONE sample (n_s % 4 != 0 is an error),  v = 4-element group inside the sample,
+ *   j = 0: the member's x_T draw;  j = 1 + state[1]: the z of a step.
+ * A member's noise is a function of (seed, m, j) alone: not of its row, of the rows beside it, or of earlier draws.
+ * members_dev: uint64 ids on the device, one per row.  Rows are n_s contiguous floats, all operands 16-byte aligned, rows <= 65535. */
+/* out[r, :] = normals of member members_dev[r] at draw index j */
+int idiff_randn_members(float* out, int R, int64_t n_s, const uint64_t* members_dev, uint64_t seed, uint64_t j, idiff_stream_t stream);
+/* row b*S + s:  cond_rep = cond[b] ;  x = 1*cond + sigma*z(member, j = 0) ;  xa = x - cond.   Bit-identical to idiff_randn_members followed
+ * by idiff_axpby(cond_rep, z, 1, sigma) and idiff_axpby(x, cond_rep, 1, -1). */
+int idiff_ensemble_init(const float* cond, float* cond_rep, float* x, float* xa, int B, int S, int64_t n_s, const uint64_t* members_dev,
+                        float sigma, uint64_t seed, idiff_stream_t stream);
+/* idiff_drift_reverse_step_dev (coef_rows = 3, r_prev = e_prev = NULL) or idiff_drift_reverse_step2_dev (coef_rows = 5) on R rows with
+ * the z of row r drawn from member members_dev[r]'s stream at j = 1 + state[1].  Same arithmetic, order and history handling; with z_base
+ * ([steps][R*n_s], indexed by state[2]) the result is bit-identical to that entry point on the same operands. */
+int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat, const float* e_hat, float* r_prev, float* e_prev, const float* z_base,
+                                         const float* cond, float* xa, int R, int64_t n_s, const float* coef, int coef_rows, int Tp1,
+                                         const int32_t* state, const uint64_t* members_dev, uint64_t seed, idiff_stream_t stream);
+/* x [B][S][n_s] -> per-pixel mean [B][n_s] and sample standard deviation std [B][n_s] over the S members, fp32, members in index order:
+ *   mean = (..((x_0 + x_1) + x_2)..)/S ;  std = sqrt((..((d_0^2 + d_1^2) + d_2^2)..)/(S - 1)),  d_s = x_s - mean ;  std = 0 for S = 1.
+ * One rounding per operation, correctly rounded quotients and root.  A thread keeps its S values in registers between the two sums for
+ * S <= 16 and reads them a second time above that (IDIFF_ENSEMBLE_REREAD=1 in the environment forces the second form; the bits are the
+ * same).  The result of image b does not depend on B. */
+int idiff_ensemble_stats(const float* x, float* mean, float* std_out, int B, int S, int64_t n_s, idiff_stream_t stream);
 /* t <- t-1 (back to T once t <= t_stop), both counters += 1, tdev[0..B) = (float)t   (the UNets' timestep input) */
 int idiff_step_state_advance(int32_t* state, float* tdev, int B, int T, int t_stop, idiff_stream_t stream);
 /* Few-step schedule form (driftSDE sample_T / sample_timesteps): t <- next_t[t] (back to t_first once t <= t_stop), both counters += 1,

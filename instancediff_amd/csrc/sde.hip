@@ -4,6 +4,9 @@
 // contraction, IEEE division, so with injected noise the result is bit-identical to the CPU reference.
 #include "common.h"
 
+#include <cstdlib>
+#include <initializer_list>
+
 // hipcc defaults to -ffp-contract=fast-honor-pragmas: without this the separate mul/sub below fuse to FMAs
 // and the result differs from the reference's op-by-op fp32 arithmetic in the last bit.
 #pragma clang fp contract(off)
@@ -34,10 +37,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f + 2.98023223876953125e-8f; }  // (0,1)
 
-// 4 standard normals for counter ctr (Box-Muller on word pairs)
-__device__ __forceinline__ floatx4 philox_normal4(uint64_t ctr, uint64_t seed) {
+// 4 standard normals for counter ctr (Box-Muller on word pairs).  member fills the upper 64 counter bits: 0 is the library's one
+// stream, m >= 1 the noise stream of ensemble member m (disjoint from stream 0 and from every other member at any ctr).
+__device__ __forceinline__ floatx4 philox_normal4(uint64_t ctr, uint64_t seed, uint64_t member = 0) {
     uint32_t w[4];
-    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)member, (uint32_t)(member >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
     const float r0 = sqrtf(-2.0f * logf(u01(w[0])));
     const float r1 = sqrtf(-2.0f * logf(u01(w[2])));
     float s0, c0, s1, c1;
@@ -385,6 +389,163 @@ void launch_irsde_map(const float* a, const float* b, const float* z, const floa
                        offset, vec4);
 }
 
+// ---- posterior ensembles: member noise streams (include/idiff.h) ----
+// Every kernel below runs on rows of n_s = 4*Q elements, grid = (chunks, rows), 16-byte aligned operands (checked on the host).
+// Row r belongs to member members[r]; its draw j uses Philox counters (j*Q + v, member) for the 4-element group v of the row:
+// nothing about a member's noise depends on the row it sits in, on the other rows, or on earlier draws of the generator.
+__global__ __launch_bounds__(256) void randn_members_kernel(float* __restrict__ out, long long Q, const uint64_t* __restrict__ members,
+                                                            uint64_t seed, uint64_t j) {
+    const uint64_t m = members[blockIdx.y];
+    floatx4* o = reinterpret_cast<floatx4*>(out) + (long long)blockIdx.y * Q;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x)
+        o[v] = philox_normal4(j * (uint64_t)Q + (uint64_t)v, seed, m);
+}
+
+// row b*S + s:  cond_rep = cond[b],  x = 1*cond + sigma*z(member, j = 0),  xa = x - cond  (axpby's products by 1 and -1 are exact)
+__global__ __launch_bounds__(256) void ensemble_init_kernel(const float* __restrict__ cond, float* __restrict__ cond_rep, float* __restrict__ x,
+                                                            float* __restrict__ xa, int S, long long Q, const uint64_t* __restrict__ members,
+                                                            float sigma, uint64_t seed) {
+    const long long row = blockIdx.y;
+    const uint64_t m = members[row];
+    const floatx4* c = reinterpret_cast<const floatx4*>(cond) + (row / S) * Q;
+    floatx4* cr = reinterpret_cast<floatx4*>(cond_rep) + row * Q;
+    floatx4* xo = reinterpret_cast<floatx4*>(x) + row * Q;
+    floatx4* xao = reinterpret_cast<floatx4*>(xa) + row * Q;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        const floatx4 cv = c[v], zv = philox_normal4((uint64_t)v, seed, m);
+        floatx4 o, oa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            o[k] = __fadd_rn(cv[k], __fmul_rn(sigma, zv[k]));
+            oa[k] = __fsub_rn(o[k], cv[k]);
+        }
+        cr[v] = cv;
+        xo[v] = o;
+        xao[v] = oa;
+    }
+}
+
+// drift_step_dev_kernel (HIST = false, coef [3][Tp1]) and drift_step2_dev_kernel (HIST = true, coef [5][Tp1]) with the z of row r
+// drawn from its member's stream at draw index j = 1 + state[1]; the arithmetic and its order are theirs.
+template <bool HIST>
+__global__ __launch_bounds__(256) void drift_step_members_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh, float* rp,
+                                                                 float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
+                                                                 float* xa, long long Q, const float* __restrict__ coef, int Tp1,
+                                                                 const int* __restrict__ state, const uint64_t* __restrict__ members,
+                                                                 uint64_t seed) {
+    const int t = state[0];
+    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
+    const float rho_d = HIST ? coef[3 * Tp1 + t] : 0.f, rho_s = HIST ? coef[4 * Tp1 + t] : 0.f;
+    const bool hist_d = HIST && rho_d != 0.f, hist_s = HIST && rho_s != 0.f;  // true for NaN too, as in drift_step2_dev_kernel
+    const uint64_t m = members[blockIdx.y];
+    const uint64_t q0 = (1ull + (uint64_t)(unsigned)state[1]) * (uint64_t)Q;
+    const long long row0 = (long long)blockIdx.y * Q;  // in 4-element groups
+    const floatx4* z = zbase ? reinterpret_cast<const floatx4*>(zbase) + (long long)state[2] * ((long long)gridDim.y * Q) + row0 : nullptr;
+    floatx4* xv4 = reinterpret_cast<floatx4*>(x) + row0;
+    floatx4* xa4 = reinterpret_cast<floatx4*>(xa) + row0;
+    const floatx4* r4 = reinterpret_cast<const floatx4*>(rh) + row0;
+    const floatx4* e4 = reinterpret_cast<const floatx4*>(eh) + row0;
+    const floatx4* c4 = reinterpret_cast<const floatx4*>(cond) + row0;
+    floatx4* rp4 = HIST ? reinterpret_cast<floatx4*>(rp) + row0 : nullptr;
+    floatx4* ep4 = HIST ? reinterpret_cast<floatx4*>(ep) + row0 : nullptr;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        const floatx4 xv = xv4[v], rv = r4[v], ev = e4[v];
+        floatx4 rt = rv, et = ev;
+        if (hist_d) {
+            const floatx4 pv = rp4[v];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
+        }
+        if (hist_s) {
+            const floatx4 pv = ep4[v];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
+        }
+        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
+        if (c != 0.f) zv = z ? z[v] : philox_normal4(q0 + (uint64_t)v, seed, m);
+        const floatx4 cv = c4[v];
+        floatx4 o, oa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
+            r = __fsub_rn(r, __fmul_rn(b, et[k]));
+            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
+            o[k] = r;
+            oa[k] = __fsub_rn(r, cv[k]);
+        }
+        xv4[v] = o;
+        xa4[v] = oa;
+        if (HIST) {
+            rp4[v] = rv;
+            ep4[v] = ev;
+        }
+    }
+}
+
+// Per-pixel mean and sample standard deviation over the S members of an image, members in index order, one rounding per operation:
+//   mean = (..((x_0 + x_1) + x_2)..) / S,   std = sqrt((..((d_0^2 + d_1^2) + d_2^2)..) / (S - 1)),  d_s = x_s - mean   (std = 0 for S = 1).
+// REG keeps a thread's S <= ENS_REG float4 values in registers between the two sums; otherwise they are read a second time.  Both do
+// the same operations in the same order.  Quotients and the root go through fp64 and are rounded to fp32 (correctly rounded, as in
+// irsde_step_kernel).
+constexpr int ENS_REG = 16;
+template <bool REG>
+__global__ __launch_bounds__(256) void ensemble_stats_kernel(const float* __restrict__ x, float* __restrict__ mean, float* __restrict__ sd, int S,
+                                                             long long Q) {
+    const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (long long)blockIdx.y * S * Q;
+    floatx4* mo = reinterpret_cast<floatx4*>(mean) + (long long)blockIdx.y * Q;
+    floatx4* so = reinterpret_cast<floatx4*>(sd) + (long long)blockIdx.y * Q;
+    const double dS = (double)S, dS1 = (double)(S - 1);
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        floatx4 val[REG ? ENS_REG : 1];
+        floatx4 acc = xs[v];
+        if (REG) {
+            val[0] = acc;
+#pragma unroll
+            for (int s = 1; s < ENS_REG; ++s)
+                if (s < S) val[s] = xs[(long long)s * Q + v];
+#pragma unroll
+            for (int s = 1; s < ENS_REG; ++s)
+                if (s < S)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], val[s][k]);
+        } else {
+            for (int s = 1; s < S; ++s) {
+                const floatx4 xv = xs[(long long)s * Q + v];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], xv[k]);
+            }
+        }
+        floatx4 mv, ss = {0.f, 0.f, 0.f, 0.f}, sv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mv[k] = (float)((double)acc[k] / dS);
+        if (REG) {
+#pragma unroll
+            for (int s = 0; s < ENS_REG; ++s)
+                if (s < S)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float d = __fsub_rn(val[s][k], mv[k]);
+                        ss[k] = s == 0 ? __fmul_rn(d, d) : __fadd_rn(ss[k], __fmul_rn(d, d));
+                    }
+        } else {
+            for (int s = 0; s < S; ++s) {
+                const floatx4 xv = xs[(long long)s * Q + v];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = __fsub_rn(xv[k], mv[k]);
+                    ss[k] = s == 0 ? __fmul_rn(d, d) : __fadd_rn(ss[k], __fmul_rn(d, d));
+                }
+            }
+        }
+        if (S > 1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sv[k] = (float)sqrt((double)(float)((double)ss[k] / dS1));  // fp64 sqrt of an fp32 value, rounded once more: correctly rounded
+        }
+        mo[v] = mv;
+        so[v] = sv;
+    }
+}
+
 inline int stream_grid(long long nvec) {
     long long g = (nvec + 255) / 256;
     if (g < 1) g = 1;
@@ -541,5 +702,88 @@ extern "C" int idiff_mix3_per_sample(const float* x0, const float* cond, const f
     dim3 grid(stream_grid(per_sample), B);
     hipLaunchKernelGGL(mix3_kernel, grid, dim3(256), 0, (hipStream_t)stream, x0, cond, eps, c0, c1, c2, out, (long long)per_sample);
     IDIFF_CHECK_LAUNCH("mix3_per_sample");
+    return IDIFF_OK;
+}
+
+// ---- posterior ensembles ----
+namespace {
+inline bool aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t bits = 0;
+    for (const void* p : ps) bits |= (uintptr_t)p;
+    return bits % 16 == 0;
+}
+inline dim3 rows_grid(long long Q, long long rows) {  // enough blocks over all rows to fill the device, at most 2048 per row
+    long long gx = (Q + 255) / 256;
+    if (gx > 2048) gx = 2048;
+    return dim3((unsigned)(gx < 1 ? 1 : gx), (unsigned)rows);
+}
+}  // namespace
+
+extern "C" int idiff_randn_members(float* out, int R, int64_t n_s, const uint64_t* members_dev, uint64_t seed, uint64_t j,
+                                   idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(out && members_dev && R > 0 && R <= 65535 && n_s > 0, "randn_members: bad args");
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "randn_members: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({out}), "randn_members: out must be 16-byte aligned");
+    hipLaunchKernelGGL(randn_members_kernel, rows_grid(n_s / 4, R), dim3(256), 0, (hipStream_t)stream, out, (long long)(n_s / 4), members_dev, seed,
+                       j);
+    IDIFF_CHECK_LAUNCH("randn_members");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_ensemble_init(const float* cond, float* cond_rep, float* x, float* xa, int B, int S, int64_t n_s,
+                                   const uint64_t* members_dev, float sigma, uint64_t seed, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(cond && cond_rep && x && xa && members_dev && B > 0 && S > 0 && (long long)B * S <= 65535 && n_s > 0,
+                    "ensemble_init: bad args");
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "ensemble_init: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({cond, cond_rep, x, xa}), "ensemble_init: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(cond_rep != x && cond_rep != xa && x != xa && cond != cond_rep && cond != x && cond != xa,
+                    "ensemble_init: operands must be distinct");
+    hipLaunchKernelGGL(ensemble_init_kernel, rows_grid(n_s / 4, (long long)B * S), dim3(256), 0, (hipStream_t)stream, cond, cond_rep, x, xa, S,
+                       (long long)(n_s / 4), members_dev, sigma, seed);
+    IDIFF_CHECK_LAUNCH("ensemble_init");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat, const float* e_hat, float* r_prev, float* e_prev,
+                                                    const float* z_base, const float* cond, float* xa, int R, int64_t n_s, const float* coef,
+                                                    int coef_rows, int Tp1, const int32_t* state, const uint64_t* members_dev, uint64_t seed,
+                                                    idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(x && r_hat && e_hat && cond && xa && coef && state && members_dev && R > 0 && R <= 65535 && n_s > 0 && Tp1 > 1,
+                    "drift_reverse_step_members_dev: bad args");
+    IDIFF_CHECK_ARG(coef_rows == 3 || coef_rows == 5, "drift_reverse_step_members_dev: coef_rows must be 3 or 5, got %d", coef_rows);
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "drift_reverse_step_members_dev: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa}),
+                    "drift_reverse_step_members_dev: operands must be 16-byte aligned");
+    const dim3 grid = rows_grid(n_s / 4, R);
+    const long long Q = n_s / 4;
+    if (coef_rows == 3) {
+        IDIFF_CHECK_ARG(!r_prev && !e_prev, "drift_reverse_step_members_dev: coef_rows = 3 takes no history buffers");
+        hipLaunchKernelGGL(drift_step_members_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond,
+                           xa, Q, coef, Tp1, state, members_dev, seed);
+    } else {
+        IDIFF_CHECK_ARG(r_prev && e_prev, "drift_reverse_step_members_dev: coef_rows = 5 needs the history buffers");
+        IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_hat && r_prev != e_hat && e_prev != r_hat && e_prev != e_hat && r_prev != x &&
+                            e_prev != x && r_prev != xa && e_prev != xa,
+                        "drift_reverse_step_members_dev: the history buffers must be distinct from each other and from every other operand");
+        hipLaunchKernelGGL(drift_step_members_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond,
+                           xa, Q, coef, Tp1, state, members_dev, seed);
+    }
+    IDIFF_CHECK_LAUNCH("drift_reverse_step_members_dev");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_ensemble_stats(const float* x, float* mean, float* std_out, int B, int S, int64_t n_s, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(x && mean && std_out && B > 0 && B <= 65535 && S > 0 && n_s > 0, "ensemble_stats: bad args");
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "ensemble_stats: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({x, mean, std_out}), "ensemble_stats: operands must be 16-byte aligned");
+    const long long Q = n_s / 4;
+    // IDIFF_ENSEMBLE_REREAD=1 (tests): the second-read form also where the values would fit in registers
+    const char* rr = getenv("IDIFF_ENSEMBLE_REREAD");
+    const bool reg = S <= ENS_REG && !(rr && rr[0] == '1');
+    if (reg)
+        hipLaunchKernelGGL(ensemble_stats_kernel<true>, rows_grid(Q, B), dim3(256), 0, (hipStream_t)stream, x, mean, std_out, S, Q);
+    else
+        hipLaunchKernelGGL(ensemble_stats_kernel<false>, rows_grid(Q, B), dim3(256), 0, (hipStream_t)stream, x, mean, std_out, S, Q);
+    IDIFF_CHECK_LAUNCH("ensemble_stats");
     return IDIFF_OK;
 }

@@ -20,6 +20,10 @@ t*sample_scale no timestep rescaling is needed.  Training (forward_diffusion) is
 Second-order multistep solver (`solver_order: 2`): the deterministic reverse path is the quadrature dx = R_hat dd + eps_hat dsigma,
 so each jump extrapolates the two predictions linearly from the previous jump's, each in its own clock (two-step Adams-Bashforth with
 variable steps), at no extra network evaluation.  It always runs the schedule path; order 1 (the default) is the update above, unchanged.
+
+Posterior ensembles (`num_samples: S`): reverse_ddpm_ensemble draws S samples per input as rows of one batched chain and
+reduces them on the device to a per-pixel mean and standard deviation.  Each row is a *member* whose noise comes from a Philox stream
+of its own, a function of (seed, member id, draw index) only, so a member's image does not depend on the batch it was computed in.
 """
 import math
 import numbers
@@ -96,6 +100,21 @@ def _solver_order(order):
     return int(order)
 
 
+def _num_samples(num):
+    """ensemble size as an int >= 1 (None: 1, off); bools, floats and strings are refused like solver_order's"""
+    if num is None:
+        return 1
+    if not isinstance(num, numbers.Integral) or isinstance(num, bool) or num < 1:
+        raise ValueError(f"driftSDE: num_samples must be an int >= 1 (or None: off), got {num!r}")
+    return int(num)
+
+
+def _max_batch(rows):
+    if not isinstance(rows, numbers.Integral) or isinstance(rows, bool) or rows < 1:
+        raise ValueError(f"driftSDE: max_batch must be an int >= 1, got {rows!r}")
+    return int(rows)
+
+
 def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
     """Device tables of a schedule: coef [3, T+1] fp32 holds the jump t_k -> t_{k+1} in row t_k (k < K) and NaN in every other row;
     next_t int32 [T+1] maps t_k to t_{k+1} and every other t to -1.  The expressions and their order are _step_coeffs' with t-1
@@ -127,7 +146,7 @@ def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
 
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
-                 sample_T=None, sample_timesteps=None, solver_order=None, **_ignored):
+                 sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -149,6 +168,16 @@ class driftSDE:
         self._jump = None  # ((timesteps, eta, order), coef, next_t) of the last schedule whose tables were built
         self.solver_order = _solver_order(solver_order)
         self.set_sample_steps(sample_T, sample_timesteps)
+        self.num_samples = _num_samples(num_samples)
+        self.max_batch = _max_batch(max_batch)
+        self._member_base = 1  # next unassigned member id; 0 is the stream of _randn_like and the plain chain
+        self.last_members = None
+
+    def set_num_samples(self, num_samples=None, max_batch=None):
+        """S members per input for reverse_ddpm_ensemble (None / 1: off -- model.test() then runs reverse_ddpm); max_batch: rows per chain"""
+        self.num_samples = _num_samples(num_samples)
+        if max_batch is not None:
+            self.max_batch = _max_batch(max_batch)
 
     def set_solver_order(self, order=None):
         """1 (or None): the first-order jump; 2: the second-order multistep jump (reverse_ddpm only, like set_sample_steps)"""
@@ -185,6 +214,7 @@ class driftSDE:
         self.seed = int(seed)
         self._calls = 0
         self._off = 0
+        self._member_base = 1
 
     def _randn_like(self, x):
         off = self._off
@@ -256,14 +286,18 @@ class driftSDE:
         streams, the fused update and the state advance; the host does not touch the loop between replays.
         `timesteps` (a few-step schedule t_0 > ... > t_K = 0) swaps in the schedule's jump tables and the table-driven state advance;
         without it the plain t -> t-1 chain runs.  `solver_order` = 2 (needs `timesteps`) swaps in the second-order update, its
-        5-row table and the two history buffers it keeps between replays."""
+        5-row table and the two history buffers it keeps between replays.
+        `members` (int64 [rows] on the device, ops.member_ids) swaps in the member step: row r draws its z from member members[r]'s own
+        stream, and the run consumes none of the sde's stream (`_off`, `_calls` stay).  `xa` hands in an x - cond already formed
+        (ops.ensemble_init)."""
 
         def __init__(self, sde, x, cond, names, text_encoder, image_context, noises=None, t_start=None, t_stop=0, timesteps=None,
-                     solver_order=1):
+                     solver_order=1, members=None, xa=None):
             self.sde, self.names, self.text_encoder, self.ctx = sde, names, text_encoder, image_context
             dev = x.device
             self.x, self.cond = x, cond
-            self.xa = ops.axpby(x, cond, 1.0, -1.0)
+            self.members = members
+            self.xa = ops.axpby(x, cond, 1.0, -1.0) if xa is None else xa
             self.T, self.t_stop = sde.T, int(t_stop)
             self.order = _solver_order(solver_order)
             if self.order == 2 and timesteps is None:
@@ -294,7 +328,11 @@ class driftSDE:
         def _body(self):
             sde = self.sde
             r_hat, e_hat = sde.predict(self.xa, self.x, self.cond, self.tdev, self.names, self.text_encoder, self.ctx)
-            if self.order == 2:
+            if self.members is not None:
+                hist = (self.r_prev, self.e_prev) if self.order == 2 else (None, None)
+                ops.drift_reverse_step_members_dev(self.x, r_hat, e_hat, hist[0], hist[1], self.noises, self.cond, self.xa, self.coef, self.state,
+                                                   self.members, sde.seed)
+            elif self.order == 2:
                 ops.drift_reverse_step2_dev(self.x, r_hat, e_hat, self.r_prev, self.e_prev, self.noises, self.cond, self.xa, self.coef, self.state,
                                             sde.seed, self.nper, self.off_base)
             else:
@@ -337,8 +375,7 @@ class driftSDE:
                 return 0
             self._warm_step()
             self.steps_done += 1
-            sde._calls += 1
-            sde._off += self.nper
+            self._account(1)
             try:
                 self.graph = self._capture()
             except Exception as e:  # stay on the eager HIP path (same kernels), say why once
@@ -361,23 +398,22 @@ class driftSDE:
                 for _ in range(nsteps):
                     self._body()
             self.steps_done += nsteps
-            sde._calls += nsteps
-            sde._off += nsteps * self.nper
+            self._account(nsteps)
             return self.x
+
+        def _account(self, nsteps):
+            """the sde's Philox accounting of nsteps steps; member runs draw from their own streams and leave it alone"""
+            if self.members is None:
+                self.sde._calls += nsteps
+                self.sde._off += nsteps * self.nper
 
         @property
         def mode(self):
             """'graph' when the loop replays a captured HIP graph, 'eager' otherwise (reported by bench.py)"""
             return "graph" if self.graph else "eager"
 
-    @torch.no_grad()
-    def reverse_ddpm(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None, x_T=None,
-                     noises=None, T_stop=0):
-        """Iterative denoising from x_T = cond + max_sigma*z down to t=1.  `noises` (optional, [T, ...]) injects
-        the per-step draws (parity runs; noises[i] is used at loop iteration i, t = T-i); x_T optional.
-        With a few-step schedule (sample_T / sample_timesteps) the loop runs K = len(timesteps) - 1 jumps t_k -> t_{k+1}, noises is
-        [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran.
-        solver_order = 2 always runs the schedule path (T, T-1, ..., 0 when no schedule is set).  self.last_solver_order: the order that ran."""
+    def _chain_plan(self, reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm"):
+        """-> (schedule or None, steps, solver order) of a reverse chain down to T_stop, after the option checks"""
         if optimize_type not in ("inputRes", "predict_noise", ""):
             raise NotImplementedError(f"optimize_type={optimize_type!r}: only the active 'inputRes' path of the reference "
                                       "(drift_noise_model.py:231-232) is in scope")
@@ -389,10 +425,23 @@ class driftSDE:
         sched = self._sched if (self._sched is not None or order == 1) else self.timesteps
         if sched is not None:
             if T_stop not in sched:
-                raise ValueError(f"reverse_ddpm: T_stop={T_stop} is not a point of the schedule {sched}")
+                raise ValueError(f"{who}: T_stop={T_stop} is not a point of the schedule {sched}")
             nsteps = sched.index(T_stop)
             if noises is not None and noises.shape[0] < nsteps:
-                raise ValueError(f"reverse_ddpm: noises holds {noises.shape[0]} draws for a {nsteps}-step chain")
+                raise ValueError(f"{who}: noises holds {noises.shape[0]} draws for a {nsteps}-step chain")
+        else:
+            nsteps = self.T - T_stop
+        return sched, nsteps, order
+
+    @torch.no_grad()
+    def reverse_ddpm(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None, x_T=None,
+                     noises=None, T_stop=0):
+        """Iterative denoising from x_T = cond + max_sigma*z down to t=1.  `noises` (optional, [T, ...]) injects
+        the per-step draws (parity runs; noises[i] is used at loop iteration i, t = T-i); x_T optional.
+        With a few-step schedule (sample_T / sample_timesteps) the loop runs K = len(timesteps) - 1 jumps t_k -> t_{k+1}, noises is
+        [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran.
+        solver_order = 2 always runs the schedule path (T, T-1, ..., 0 when no schedule is set).  self.last_solver_order: the order that ran."""
+        sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop)
         cond = cond.contiguous()
         B = cond.shape[0]
         if x_T is None:
@@ -400,7 +449,6 @@ class driftSDE:
         x = x_T.contiguous().clone()
         if sched is None:
             stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
-            nsteps = self.T - T_stop
         else:
             stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched,
                                        solver_order=order)
@@ -409,3 +457,52 @@ class driftSDE:
         self.last_steps = nsteps
         self.last_solver_order = order
         return out
+
+    def _assign_members(self, B, S, members):
+        """ids of the B*S rows (row b*S + s): explicit `members` ([B*S] or [B, S] ints >= 1, no duplicates) or the next B*S of the
+        sde's counter, which starts at 1, is reset by set_seed and is left alone by explicit ids"""
+        if members is None:
+            ids = list(range(self._member_base, self._member_base + B * S))
+            self._member_base += B * S
+            return ids
+        ids = torch.as_tensor(members).reshape(-1).tolist()
+        if len(ids) != B * S or any(not isinstance(m, int) or isinstance(m, bool) or m < 1 for m in ids) or len(set(ids)) != len(ids):
+            raise ValueError(f"reverse_ddpm_ensemble: members must be {B * S} distinct ints >= 1 (0 is the sde's own stream), got {ids}")
+        return ids
+
+    @torch.no_grad()
+    def reverse_ddpm_ensemble(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None,
+                              num_samples=None, members=None, noises=None, T_stop=0, return_samples=False):
+        """S posterior samples per input row as one batched chain -> (mean [B, ...], std [B, ...][, samples [B, S, ...]]).
+        Row b*S + s is member m(b, s), whose x_T draw and per-step z come from its own Philox stream (include/idiff.h): its image is the
+        same in any batch, chunking or call order.  The B*S rows run in chunks of at most max_batch rows, each through a Stepper of its
+        own (schedule, solver_order, warm step, capture and T_stop as in reverse_ddpm), and are reduced on the device.  `noises`
+        ([steps, B*S, ...]) injects the per-step draws.  self.last_members: the ids used, [B, S]."""
+        S = self.num_samples if num_samples is None else _num_samples(num_samples)
+        sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_ensemble")
+        cond = cond.contiguous()
+        B = cond.shape[0]
+        R = B * S
+        if (cond.numel() // B) % 4:
+            raise ValueError(f"reverse_ddpm_ensemble: a sample has {cond.numel() // B} elements, not a multiple of 4")
+        if noises is not None and (noises.dim() < 2 or noises.shape[1] != R):
+            raise ValueError(f"reverse_ddpm_ensemble: noises must be [steps, B*S = {R}, ...], got {tuple(noises.shape)}")
+        ids = self._assign_members(B, S, members)
+        mdev = ops.member_ids(ids, cond.device)
+        cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
+        names_rep = [n for n in names for _ in range(S)]
+        ctx_rep = None if image_context is None else image_context.repeat_interleave(S, dim=0)
+        for r0 in range(0, R, self.max_batch):
+            r1 = min(r0 + self.max_batch, R)
+            stepper = driftSDE.Stepper(self, x[r0:r1], cond_rep[r0:r1], names_rep[r0:r1], text_encoder,
+                                       None if ctx_rep is None else ctx_rep[r0:r1].contiguous(),
+                                       noises=None if noises is None else noises[:, r0:r1].contiguous(), t_stop=T_stop, timesteps=sched,
+                                       solver_order=order, members=mdev[r0:r1], xa=xa[r0:r1])
+            stepper.run(nsteps)
+        self.last_mode = stepper.mode
+        self.last_steps = nsteps
+        self.last_solver_order = order
+        self.last_members = torch.tensor(ids, dtype=torch.int64).view(B, S)
+        samples = x.view((B, S) + tuple(cond.shape[1:]))
+        mean, std = ops.ensemble_stats(samples)
+        return (mean, std, samples) if return_samples else (mean, std)

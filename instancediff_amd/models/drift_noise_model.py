@@ -216,8 +216,17 @@ class CLIPDriftModel():
     # ---- sampling ----------------------------------------------------------------------------------
     @torch.no_grad()
     def test(self, **kw):  # :648-652
-        out = self.sde.reverse_ddpm(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
-                                    optimize_type=self.optimize_type, image_context=self.A_emb, **kw)
+        """one restoration per input; with sde.num_samples > 1 (driftSDE) a posterior ensemble: output / get_visuals() are the per-pixel
+        mean of the members, output_std their spread, samples the members [B, S, ...] when called with return_samples=True"""
+        self.output_std = self.samples = None
+        if getattr(self.sde, "num_samples", 1) > 1:
+            res = self.sde.reverse_ddpm_ensemble(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
+                                                 optimize_type=self.optimize_type, image_context=self.A_emb, **kw)
+            out, self.output_std = res[0], res[1]
+            self.samples = res[2] if len(res) > 2 else None
+        else:
+            out = self.sde.reverse_ddpm(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
+                                        optimize_type=self.optimize_type, image_context=self.A_emb, **kw)
         self.output = out
         self.visuals = out.detach().cpu().numpy()
 

@@ -802,6 +802,72 @@ def drift_reverse_step2_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, c
           "drift_reverse_step2_dev")
 
 
+# ---- posterior ensembles: member noise streams (include/idiff.h) ----
+def member_ids(members, device):
+    """ids (ints >= 1, any nesting flattened by the caller) -> int64 [R] on the device: the uint64 words the kernels read.  Id 0 is
+    the stream of randn() and the plain steps and is refused, as are ids that do not fit 63 bits."""
+    ids = [int(m) for m in members]
+    if not ids or any(m < 1 or m >= 1 << 63 for m in ids):
+        raise ValueError(f"member ids must be ints in [1, 2**63), got {ids}")
+    return torch.tensor(ids, dtype=torch.int64, device=device)
+
+
+def _members(members, rows):
+    _c(members, "members", torch.int64)
+    if members.dim() != 1 or members.numel() != rows:
+        raise _lib.IdiffError(f"members must be int64 [{rows}], got {tuple(members.shape)}")
+    return C.c_void_p(members.data_ptr())
+
+
+def randn_members(members, sample_shape, seed, j=0):
+    """[R, *sample_shape] normals: row r is draw j of member members[r] (int64 [R] on the device, from member_ids())"""
+    lib = _lib.load()
+    R = members.numel()
+    out = torch.empty((R,) + tuple(sample_shape), device=members.device, dtype=torch.float32)
+    check(lib.idiff_randn_members(_p(out), R, out.numel() // R, _members(members, R), seed, j, _stream()), "randn_members")
+    return out
+
+
+def ensemble_init(cond, S, members, sigma, seed):
+    """cond [B, ...] -> (cond_rep, x, xa), each [B*S, ...]: row b*S + s holds cond[b], cond[b] + sigma*z(member, j = 0), x - cond[b]"""
+    lib = _lib.load()
+    _c(cond, "cond")
+    B = cond.shape[0]
+    cond_rep = torch.empty((B * S,) + tuple(cond.shape[1:]), device=cond.device, dtype=torch.float32)
+    x, xa = torch.empty_like(cond_rep), torch.empty_like(cond_rep)
+    check(lib.idiff_ensemble_init(_p(cond), _p(cond_rep), _p(x), _p(xa), B, S, cond.numel() // B, _members(members, B * S), sigma, seed,
+                                  _stream()), "ensemble_init")
+    return cond_rep, x, xa
+
+
+def drift_reverse_step_members_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, coef, state, members, seed):
+    """drift_reverse_step_dev (coef [3, T+1], r_prev = e_prev = None) or drift_reverse_step2_dev (coef [5, T+1]) on the rows of x
+    [R, ...], with row r's z from member members[r]'s stream at draw 1 + state[1] (or from z_base [steps, R, ...])"""
+    lib = _lib.load()
+    _c(x, "x"), _c(r_hat, "r_hat"), _c(e_hat, "e_hat"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
+    _c(xa, "xa"), _c(coef, "coef"), _c(state, "state", torch.int32)
+    R = x.shape[0]
+    assert state.numel() == 3 and coef.dim() == 2 and coef.shape[0] in (3, 5)
+    for t in (r_hat, e_hat, r_prev, e_prev, cond, xa):
+        assert t is None or t.numel() == x.numel()
+    assert z_base is None or z_base.numel() % x.numel() == 0
+    check(lib.idiff_drift_reverse_step_members_dev(_p(x), _p(r_hat), _p(e_hat), _p(r_prev), _p(e_prev), _p(z_base), _p(cond), _p(xa), R,
+                                                   x.numel() // R, _p(coef), coef.shape[0], coef.shape[1], C.c_void_p(state.data_ptr()),
+                                                   _members(members, R), seed, _stream()), "drift_reverse_step_members_dev")
+
+
+def ensemble_stats(x):
+    """x [B, S, ...] -> (mean, std), each [B, ...]: per-pixel mean and sample standard deviation over the S members, one pass"""
+    lib = _lib.load()
+    _c(x, "x")
+    assert x.dim() >= 3, "ensemble_stats: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    mean = torch.empty((B,) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+    std = torch.empty_like(mean)
+    check(lib.idiff_ensemble_stats(_p(x), _p(mean), _p(std), B, S, x.numel() // (B * S), _stream()), "ensemble_stats")
+    return mean, std
+
+
 def step_state_advance(state, tdev, T, t_stop=0):
     lib = _lib.load()
     _c(tdev, "tdev")

@@ -5,7 +5,8 @@
 
 Reads `test: {iter, pth_dir, use_ema, which_model, which_sde, result_root}` (testUM.py:71-100), restores every
 image of the test sets with `model.test()` (timed like :141-144), computes RMSE / PSNR / SSIM per image on the
-device (:151-164) and writes the LQ|pred|GT `.raw` triptychs (:170-173).  With `--random-init` the checkpoint load
+device (:151-164) and writes the LQ|pred|GT `.raw` triptychs (:170-173).  With `--num-samples S` (driftSDE) each image is restored as
+an S-member posterior ensemble: the metrics and the triptych are the mean's, `PSNR_member` / `STD` and a `<i>_std_WxHx1.raw` map are added.  With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
@@ -31,6 +32,11 @@ def main(argv=None):
                         help="reverse-chain steps per image (driftSDE sample_T: K uniform jumps over the T-step schedule)")
     parser.add_argument("--solver-order", type=int, default=None, metavar="N", choices=(1, 2),
                         help="driftSDE solver_order: 1 = first-order jumps, 2 = second-order multistep jumps (overrides the YAML)")
+    parser.add_argument("--num-samples", type=int, default=None, metavar="S",
+                        help="driftSDE num_samples: S posterior samples per image as one batched chain; the mean is the restored image, "
+                             "the per-pixel standard deviation is written next to it (overrides the YAML)")
+    parser.add_argument("--max-batch", type=int, default=None, metavar="M",
+                        help="driftSDE max_batch: rows per chain of an ensemble (overrides the YAML)")
     args = parser.parse_args(argv)
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
@@ -48,12 +54,20 @@ def main(argv=None):
         sde_opt['sample_T'] = args.sample_T
     if args.solver_order is not None:
         sde_opt['solver_order'] = args.solver_order
+    if args.num_samples is not None:
+        sde_opt['num_samples'] = args.num_samples
+    if args.max_batch is not None:
+        sde_opt['max_batch'] = args.max_batch
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
     model.set_eval()
+    S = getattr(sde, 'num_samples', 1)
     result_root = os.path.join(test_opt['result_root'], opt['name'])
     results = OrderedDict((a, {'num': 0, 'RMSE': [], 'SSIM': [], 'PSNR': []}) for a in opt['artifact_type'])
+    if S > 1:
+        for r in results.values():
+            r['PSNR_member'], r['STD'] = [], []
     times = []
     n_done = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -73,7 +87,7 @@ def main(argv=None):
                 model.feed_data(data)
                 torch.cuda.synchronize()
                 tic = time.time()
-                model.test()
+                model.test(**({'return_samples': True} if S > 1 else {}))
                 times.append(time.time() - tic)
                 rmse, psnr, ssim = ops.image_metrics(model.output[:, 0], model.target[:, 0]).cpu().tolist()[0]
                 r = results[it["name"]]
@@ -82,16 +96,25 @@ def main(argv=None):
                 shape = dump_raw(os.path.join(result_root, it["name"], f"{i}.raw"), it["LQ"].numpy(), model.get_visuals(), it["GT"].numpy())
                 os.replace(os.path.join(result_root, it["name"], f"{i}.raw"),
                            os.path.join(result_root, it["name"], f"{i}_{shape[-1]}x{shape[-2]}x1.raw"))
-                print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}')
+                extra = ""
+                if S > 1:  # the listed metrics are the mean's; the members' own PSNR and the spread go beside them
+                    member = ops.image_metrics(model.samples[0, :, 0], model.target[:, 0].expand(S, -1, -1).contiguous()).cpu()
+                    r['PSNR_member'].append(float(member[:, 1].mean()))
+                    std_map = model.output_std[0, 0].cpu()
+                    r['STD'].append(float(std_map.mean()))
+                    std_map.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_std_{std_map.shape[-1]}x{std_map.shape[-2]}x1.raw"))
+                    extra = f", PSNR_member={r['PSNR_member'][-1]}, STD={r['STD'][-1]}"
+                print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
                     break
     for k, v in results.items():
         if v['num']:
-            print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR')))
+            print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR') + (('PSNR_member', 'STD') if S > 1 else ())))
     if times:
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
-              + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else ""))
+              + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
+              + (f", {S} samples per image" if S > 1 else ""))
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return results
