@@ -504,6 +504,34 @@ int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat, const flo
  * S <= 16 and reads them a second time above that (IDIFF_ENSEMBLE_REREAD=1 in the environment forces the second form; the bits are the
  * same).  The result of image b does not depend on B. */
 int idiff_ensemble_stats(const float* x, float* mean, float* std_out, int B, int S, int64_t n_s, idiff_stream_t stream);
+/* ---- tiled sampling (driftSDE tile / tile_overlap) ----
+ * The chain's state is one full-resolution image [B][C][H][W]; the nets see it as a batch of ny*nx windows of Ph x Pw per image, window
+ * row ((b*ny + iy)*nx + ix), each [C][Ph][Pw] contiguous.  W, Pw and the W origins are multiples of 4; all operands 16-byte aligned.
+ * The host plan (models/SDEs/driftSDE.py, tile_plan) hands in two tables per axis of length L with n windows, on the device:
+ *   ytab / xtab  int32 [3*L + n] = first[L] | cov_lo[L] | cov_hi[L] | origin[n]
+ *   ywt  / xwt   fp32  [2*L]     = w0[L] | w1[L]
+ * first[c]: the lower of the at most two (adjacent) windows with non-zero blend weight at coordinate c; w0[c] / w1[c]: the weights of
+ * windows first[c] and first[c] + 1 (exactly 1 and 0 outside the blend zones); windows cov_lo[c] <= i < cov_hi[c] are those whose extent
+ * [origin[i], origin[i] + P) holds c.  The entry points check the sizes; the table contents are the plan's responsibility.
+ * tiles[row, c, :, :] = full[b, c, origin_y[iy] : +Ph, origin_x[ix] : +Pw]  (reads ytab / xtab's origins only) */
+int idiff_tile_gather(const float* full, float* tiles, int B, int C, int H, int W, int ny, int nx, int Ph, int Pw, const int32_t* ytab,
+                      const int32_t* xtab, idiff_stream_t stream);
+/* The step of a tiled chain, per pixel of the full image, per-step scalars from coef / state as in idiff_drift_reverse_step_dev:
+ *   R^ = blend of r_tiles over the slots (iy0, ix0), (iy0, ix1), (iy1, ix0), (iy1, ix1) in that order, iy0 = first_y, iy1 = iy0 + 1 (x alike):
+ *        w = wy*wx (one fp32 product);  acc = w*r for the first term, acc = acc + w*r after it;  a slot whose w is exactly 0 is skipped and
+ *        its memory is not read, so a singly covered pixel is 1.0f*r, exact.   e^ likewise from e_tiles.
+ *   coef_rows = 5: r_prev / e_prev [B][C][H][W] hold the previous jump's BLENDED predictions; the extrapolation, its zero-rho rule and the
+ *        hand-over (r_prev <- R^, e_prev <- e^) are idiff_drift_reverse_step2_dev's.  coef_rows = 3: r_prev = e_prev = NULL.
+ *   z  = z_base[state[2]][v] (injected, full image) or the Philox normals of counter offset_base + state[1]*nper + v, v the float4 index
+ *        in the flattened full image: the counter of idiff_drift_reverse_step_dev on that image, whatever the tiling.
+ *   x <- ((x - a*R^) - b*e^) + c*z ;  xa = x - cond ;  x and xa are then written into x_tiles / xa_tiles of every window whose extent
+ *        holds the pixel (by extent, not by weight: a window's border is filled where its weight is 0).
+ * With one window per pixel the full-image x is bit-identical to idiff_drift_reverse_step_dev / _step2_dev on the gathered operands. */
+int idiff_drift_reverse_step_tiled_dev(float* x, const float* r_tiles, const float* e_tiles, float* r_prev, float* e_prev, const float* z_base,
+                                       const float* cond, float* x_tiles, float* xa_tiles, int B, int C, int H, int W, int ny, int nx, int Ph,
+                                       int Pw, const int32_t* ytab, const float* ywt, const int32_t* xtab, const float* xwt, const float* coef,
+                                       int coef_rows, int Tp1, const int32_t* state, uint64_t seed, uint64_t nper, uint64_t offset_base,
+                                       idiff_stream_t stream);
 /* t <- t-1 (back to T once t <= t_stop), both counters += 1, tdev[0..B) = (float)t   (the UNets' timestep input) */
 int idiff_step_state_advance(int32_t* state, float* tdev, int B, int T, int t_stop, idiff_stream_t stream);
 /* Few-step schedule form (driftSDE sample_T / sample_timesteps): t <- next_t[t] (back to t_first once t <= t_stop), both counters += 1,

@@ -546,6 +546,162 @@ __global__ __launch_bounds__(256) void ensemble_stats_kernel(const float* __rest
     }
 }
 
+// ---- tiled sampling (driftSDE tile / tile_overlap) ----
+// The state is ONE full-resolution image [B][C][H][W]; the nets see it as a batch of Ph x Pw windows, row ((b*ny + iy)*nx + ix).
+// Per axis of length L the host plan gives an int32 table {first[L], cov_lo[L], cov_hi[L], origin[n]} and an fp32 table {w0[L], w1[L]}:
+// first = the lower of the (at most two, adjacent) windows with non-zero blend weight at a coordinate, w0 / w1 their weights, and
+// [cov_lo, cov_hi) the windows whose extent holds the coordinate.  W, Pw and the W origins are multiples of 4, so a float4 group
+// never straddles a window edge and `first` and the coverage are uniform over it.
+struct TileGeom {
+    int C, H, W4, ny, nx, Ph, Pw4;
+    const int* yi;    // first | cov_lo | cov_hi | origin, over H
+    const int* xi;    // the same over W (element coordinates)
+    const float* yw;  // w0 | w1 over H
+    const float* xw;  // w0 | w1 over W
+};
+
+// float4 index inside the tile buffers of pixel group (bc = b*C + c, y, x4) seen from window (iy, ix)
+__device__ __forceinline__ long long tile_at(const TileGeom& g, long long b, int c, int y, int x4, int iy, int ix) {
+    const int H = g.H, W = g.W4 * 4;
+    const int ly = y - g.yi[3 * H + iy], lx4 = x4 - (g.xi[3 * W + ix] >> 2);
+    return ((((b * g.ny + iy) * g.nx + ix) * g.C + c) * g.Ph + ly) * g.Pw4 + lx4;
+}
+
+__global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restrict__ full, float* __restrict__ tiles, long long nvt, TileGeom g) {
+    const floatx4* f4 = reinterpret_cast<const floatx4*>(full);
+    floatx4* t4 = reinterpret_cast<floatx4*>(tiles);
+    const int H = g.H, W = g.W4 * 4;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nvt; v += (long long)gridDim.x * blockDim.x) {
+        const long long trow = v / g.Pw4;
+        const int lx4 = (int)(v - trow * g.Pw4);
+        const long long tc = trow / g.Ph;
+        const int ly = (int)(trow - tc * g.Ph);
+        const long long win = tc / g.C;
+        const int c = (int)(tc - win * g.C);
+        const long long by = win / g.nx;
+        const int ix = (int)(win - by * g.nx);
+        const long long b = by / g.ny;
+        const int iy = (int)(by - b * g.ny);
+        const int y = g.yi[3 * H + iy] + ly, x4 = (g.xi[3 * W + ix] >> 2) + lx4;
+        t4[v] = f4[((b * g.C + c) * H + y) * g.W4 + x4];
+    }
+}
+
+// One slot of the blend: acc = w*r for the first term of an element, acc + w*r after it; an element whose weight is exactly 0 takes
+// nothing from the slot, and a slot whose four weights are all 0 is not read.
+__device__ __forceinline__ void blend_slot(const floatx4* __restrict__ src, long long at, float wy, floatx4 wx, floatx4& acc, bool (&have)[4]) {
+    floatx4 w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = __fmul_rn(wy, wx[k]);
+    if (w[0] == 0.f && w[1] == 0.f && w[2] == 0.f && w[3] == 0.f) return;
+    const floatx4 rv = src[at];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (w[k] == 0.f) continue;
+        const float p = __fmul_rn(w[k], rv[k]);
+        acc[k] = have[k] ? __fadd_rn(acc[k], p) : p;
+        have[k] = true;
+    }
+}
+
+// The tiled step.  Per float4 group v of the full image: blend the windows' predictions into R^ and e^ (slots (iy0,ix0), (iy0,ix1),
+// (iy1,ix0), (iy1,ix1) in that order, weight wy*wx), extrapolate them as drift_step2_dev_kernel does when HIST, draw z at the plain
+// chain's counter offset + v, update as drift_step_dev_kernel does, and scatter x and x - cond into every window whose extent holds
+// the group.  Element-wise per pixel: a thread reads and writes only its own group of x / rp / ep and of each window's copy of it.
+template <bool HIST>
+__global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const float* __restrict__ rt_, const float* __restrict__ et_, float* rp,
+                                                               float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
+                                                               float* __restrict__ xt_, float* __restrict__ xat_, long long nv, TileGeom g,
+                                                               const float* __restrict__ coef, int Tp1, const int* __restrict__ state,
+                                                               uint64_t seed, uint64_t nper, uint64_t offset_base) {
+    const int t = state[0];
+    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
+    const float rho_d = HIST ? coef[3 * Tp1 + t] : 0.f, rho_s = HIST ? coef[4 * Tp1 + t] : 0.f;
+    const bool hist_d = HIST && rho_d != 0.f, hist_s = HIST && rho_s != 0.f;  // true for NaN too, as in drift_step2_dev_kernel
+    const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
+    const floatx4* z4 = zbase ? reinterpret_cast<const floatx4*>(zbase) + (long long)state[2] * nv : nullptr;
+    floatx4* x4p = reinterpret_cast<floatx4*>(x);
+    const floatx4* c4 = reinterpret_cast<const floatx4*>(cond);
+    const floatx4* r4 = reinterpret_cast<const floatx4*>(rt_);
+    const floatx4* e4 = reinterpret_cast<const floatx4*>(et_);
+    floatx4* xt4 = reinterpret_cast<floatx4*>(xt_);
+    floatx4* xat4 = reinterpret_cast<floatx4*>(xat_);
+    floatx4* rp4 = reinterpret_cast<floatx4*>(rp);
+    floatx4* ep4 = reinterpret_cast<floatx4*>(ep);
+    const int H = g.H, W = g.W4 * 4;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
+        const long long row = v / g.W4;
+        const int xg = (int)(v - row * g.W4);
+        const long long bc = row / H;
+        const int y = (int)(row - bc * H);
+        const long long bi = bc / g.C;
+        const int ci = (int)(bc - bi * g.C);
+        const int xe = xg * 4;
+        const int iy0 = g.yi[y], ix0 = g.xi[xe];
+        const float wy0 = g.yw[y], wy1 = g.yw[H + y];
+        const floatx4 wx0 = *reinterpret_cast<const floatx4*>(g.xw + xe), wx1 = *reinterpret_cast<const floatx4*>(g.xw + W + xe);
+        const bool y1 = wy1 != 0.f;
+        const bool x1 = wx1[0] != 0.f || wx1[1] != 0.f || wx1[2] != 0.f || wx1[3] != 0.f;
+        // a slot without weight may name a window that does not exist (first + 1 == n): its address is never formed
+        const long long a00 = tile_at(g, bi, ci, y, xg, iy0, ix0);
+        const long long a01 = x1 ? tile_at(g, bi, ci, y, xg, iy0, ix0 + 1) : 0;
+        const long long a10 = y1 ? tile_at(g, bi, ci, y, xg, iy0 + 1, ix0) : 0;
+        const long long a11 = (y1 && x1) ? tile_at(g, bi, ci, y, xg, iy0 + 1, ix0 + 1) : 0;
+        const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        floatx4 rv = zero4, ev = zero4;
+        {
+            bool have[4] = {false, false, false, false};
+            blend_slot(r4, a00, wy0, wx0, rv, have);
+            if (x1) blend_slot(r4, a01, wy0, wx1, rv, have);
+            if (y1) blend_slot(r4, a10, wy1, wx0, rv, have);
+            if (y1 && x1) blend_slot(r4, a11, wy1, wx1, rv, have);
+        }
+        {
+            bool have[4] = {false, false, false, false};
+            blend_slot(e4, a00, wy0, wx0, ev, have);
+            if (x1) blend_slot(e4, a01, wy0, wx1, ev, have);
+            if (y1) blend_slot(e4, a10, wy1, wx0, ev, have);
+            if (y1 && x1) blend_slot(e4, a11, wy1, wx1, ev, have);
+        }
+        const floatx4 xv = x4p[v];
+        floatx4 rt = rv, et = ev;
+        if (hist_d) {
+            const floatx4 pv = rp4[v];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
+        }
+        if (hist_s) {
+            const floatx4 pv = ep4[v];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
+        }
+        floatx4 zv = zero4;
+        if (c != 0.f) zv = z4 ? z4[v] : philox_normal4(offset + (uint64_t)v, seed);
+        const floatx4 cv = c4[v];
+        floatx4 o, oa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
+            r = __fsub_rn(r, __fmul_rn(b, et[k]));
+            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
+            o[k] = r;
+            oa[k] = __fsub_rn(r, cv[k]);
+        }
+        x4p[v] = o;
+        if (HIST) {
+            rp4[v] = rv;
+            ep4[v] = ev;
+        }
+        const int cy0 = g.yi[H + y], cy1 = g.yi[2 * H + y], cx0 = g.xi[W + xe], cx1 = g.xi[2 * W + xe];
+        for (int iy = cy0; iy < cy1; ++iy)
+            for (int ix = cx0; ix < cx1; ++ix) {
+                const long long at = tile_at(g, bi, ci, y, xg, iy, ix);
+                xt4[at] = o;
+                xat4[at] = oa;
+            }
+    }
+}
+
 inline int stream_grid(long long nvec) {
     long long g = (nvec + 255) / 256;
     if (g < 1) g = 1;
@@ -718,6 +874,63 @@ inline dim3 rows_grid(long long Q, long long rows) {  // enough blocks over all 
     return dim3((unsigned)(gx < 1 ? 1 : gx), (unsigned)rows);
 }
 }  // namespace
+
+// ---- tiled sampling ----
+namespace {
+inline bool tile_geom(TileGeom& g, int B, int C, int H, int W, int ny, int nx, int Ph, int Pw, const int32_t* ytab, const float* ywt,
+                      const int32_t* xtab, const float* xwt, bool weights = true) {
+    if (!(ytab && xtab && (!weights || (ywt && xwt)) && B > 0 && C > 0 && H > 0 && W > 0 && ny > 0 && nx > 0 && Ph > 0 && Pw > 0)) return false;
+    if (W % 4 || Pw % 4 || Ph > H || Pw > W || (ny == 1) != (Ph == H) || (nx == 1) != (Pw == W)) return false;
+    if ((long long)ny * Ph < H || (long long)nx * Pw < W) return false;  // the windows cannot cover the image
+    g = TileGeom{C, H, W / 4, ny, nx, Ph, Pw / 4, ytab, xtab, ywt, xwt};
+    return true;
+}
+}  // namespace
+
+extern "C" int idiff_tile_gather(const float* full, float* tiles, int B, int C, int H, int W, int ny, int nx, int Ph, int Pw,
+                                 const int32_t* ytab, const int32_t* xtab, idiff_stream_t stream) {
+    TileGeom g;
+    IDIFF_CHECK_ARG(full && tiles && full != tiles && tile_geom(g, B, C, H, W, ny, nx, Ph, Pw, ytab, nullptr, xtab, nullptr, false),
+                    "tile_gather: bad args (W, Pw multiples of 4; windows inside and covering the image)");
+    IDIFF_CHECK_ARG(aligned16({full, tiles}), "tile_gather: operands must be 16-byte aligned");
+    const long long nvt = (long long)B * ny * nx * C * Ph * (Pw / 4);
+    hipLaunchKernelGGL(tile_gather_kernel, dim3(stream_grid(nvt)), dim3(256), 0, (hipStream_t)stream, full, tiles, nvt, g);
+    IDIFF_CHECK_LAUNCH("tile_gather");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_drift_reverse_step_tiled_dev(float* x, const float* r_tiles, const float* e_tiles, float* r_prev, float* e_prev,
+                                                  const float* z_base, const float* cond, float* x_tiles, float* xa_tiles, int B, int C, int H,
+                                                  int W, int ny, int nx, int Ph, int Pw, const int32_t* ytab, const float* ywt,
+                                                  const int32_t* xtab, const float* xwt, const float* coef, int coef_rows, int Tp1,
+                                                  const int32_t* state, uint64_t seed, uint64_t nper, uint64_t offset_base,
+                                                  idiff_stream_t stream) {
+    TileGeom g;
+    IDIFF_CHECK_ARG(x && r_tiles && e_tiles && cond && x_tiles && xa_tiles && coef && state && Tp1 > 1 &&
+                        tile_geom(g, B, C, H, W, ny, nx, Ph, Pw, ytab, ywt, xtab, xwt),
+                    "drift_reverse_step_tiled_dev: bad args (W, Pw multiples of 4; windows inside and covering the image)");
+    IDIFF_CHECK_ARG(coef_rows == 3 || coef_rows == 5, "drift_reverse_step_tiled_dev: coef_rows must be 3 or 5, got %d", coef_rows);
+    IDIFF_CHECK_ARG(aligned16({x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, xwt}),
+                    "drift_reverse_step_tiled_dev: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(x_tiles != xa_tiles && x_tiles != r_tiles && x_tiles != e_tiles && xa_tiles != r_tiles && xa_tiles != e_tiles &&
+                        x != x_tiles && x != xa_tiles && x != r_tiles && x != e_tiles && x != cond,
+                    "drift_reverse_step_tiled_dev: the image and the four window buffers must be distinct");
+    const long long nv = (long long)B * C * H * (W / 4);
+    if (coef_rows == 3) {
+        IDIFF_CHECK_ARG(!r_prev && !e_prev, "drift_reverse_step_tiled_dev: coef_rows = 3 takes no history buffers");
+        hipLaunchKernelGGL(drift_step_tiled_kernel<false>, dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev,
+                           e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed, nper, offset_base);
+    } else {
+        IDIFF_CHECK_ARG(r_prev && e_prev, "drift_reverse_step_tiled_dev: coef_rows = 5 needs the history buffers");
+        IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_tiles && r_prev != e_tiles && e_prev != r_tiles && e_prev != e_tiles && r_prev != x &&
+                            e_prev != x && r_prev != x_tiles && e_prev != x_tiles && r_prev != xa_tiles && e_prev != xa_tiles,
+                        "drift_reverse_step_tiled_dev: the history buffers must be distinct from each other and from every other operand");
+        hipLaunchKernelGGL(drift_step_tiled_kernel<true>, dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev,
+                           e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed, nper, offset_base);
+    }
+    IDIFF_CHECK_LAUNCH("drift_reverse_step_tiled_dev");
+    return IDIFF_OK;
+}
 
 extern "C" int idiff_randn_members(float* out, int R, int64_t n_s, const uint64_t* members_dev, uint64_t seed, uint64_t j,
                                    idiff_stream_t stream) {

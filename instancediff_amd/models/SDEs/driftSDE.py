@@ -24,6 +24,11 @@ variable steps), at no extra network evaluation.  It always runs the schedule pa
 Posterior ensembles (`num_samples: S`): reverse_ddpm_ensemble draws S samples per input as rows of one batched chain and
 reduces them on the device to a per-pixel mean and standard deviation.  Each row is a *member* whose noise comes from a Philox stream
 of its own, a function of (seed, member id, draw index) only, so a member's image does not depend on the batch it was computed in.
+
+Tiled sampling (`tile` / `tile_overlap`): an image larger than the window the nets are built for runs as a batch of
+overlapping windows.  The state stays ONE full-resolution image: every step blends the windows' two predictions into full-image R_hat and
+eps_hat, updates and draws the noise once per pixel on the full image (the plain chain's Philox counters, whatever the tiling), and cuts the
+next step's window inputs out again -- one fused kernel per step beside the nets.
 """
 import math
 import numbers
@@ -115,6 +120,114 @@ def _max_batch(rows):
     return int(rows)
 
 
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _tile_size(tile):
+    """window size of tiled sampling as (Ph, Pw), or None (off).  `tile` is an int P or a pair [Ph, Pw] of ints, each a positive multiple
+    of 4; bools, floats and strings are refused like solver_order's"""
+    if tile is None:
+        return None
+    pair = list(tile) if isinstance(tile, (list, tuple)) else [tile, tile]
+    if len(pair) != 2 or not all(_is_int(p) and p >= 4 and p % 4 == 0 for p in pair):
+        raise ValueError(f"driftSDE: tile must be an int P or a pair [Ph, Pw] of positive multiples of 4 (or None: off), got {tile!r}")
+    return int(pair[0]), int(pair[1])
+
+
+def _tile_overlap(overlap, P):
+    """overlap of adjacent windows of size P along one axis: a multiple of 4 in [0, P // 2]; None: P // 8 rounded down to a multiple of 4"""
+    if overlap is None:
+        return (P // 8) // 4 * 4
+    if not _is_int(overlap) or overlap % 4 != 0 or not 0 <= overlap <= P // 2:
+        raise ValueError(f"driftSDE: tile_overlap must be an int multiple of 4 in [0, tile // 2 = {P // 2}] (or None: tile // 8), got {overlap!r}")
+    return int(overlap)
+
+
+def tile_axis_plan(L, P, O, align=1):
+    """The windows of one axis of length L (window P, overlap O; origins rounded down to a multiple of `align`: 4 on the W axis) and
+    their blend -> dict(n, P, origins, zones, first, w0, w1, cov_lo, cov_hi), the per-coordinate tables as numpy arrays of length L.
+      * L <= P: one window of length L at 0.  Otherwise n = ceil((L - O) / (P - O)) windows at o_i = (i * (L - P)) // (n - 1): o_0 = 0,
+        o_{n-1} = L - P, every stride in (0, P - O].
+      * windows i and i+1 blend over the zone [o_{i+1}, min(o_i + P, o_{i+2})) (o_n = inf): a coordinate never has more than two windows
+        with non-zero weight, and they are adjacent, also where three windows overlap physically.  At the k-th coordinate of a zone of
+        length z window i+1 weighs beta = (k + 0.5) / z and window i 1 - beta, in fp64, each rounded once to fp32.
+      * first[c]: the lower window with weight at c, w0 / w1 the weights of windows first and first + 1: exactly 1.0 and 0.0 outside zones.
+      * cov_lo[c] <= i < cov_hi[c]: the windows whose extent [o_i, o_i + P) holds c (the scatter's targets)."""
+    import numpy as np
+    if not (L >= 1 and P >= 1 and 0 <= O <= P // 2 and align >= 1):
+        raise ValueError(f"tile_axis_plan: bad arguments L={L}, P={P}, O={O}, align={align}")
+    if L <= P:
+        n, ext, origins = 1, L, [0]
+    else:
+        n = -((O - L) // (P - O))
+        ext = P
+        origins = [((i * (L - P)) // (n - 1)) // align * align for i in range(n)]
+    first = np.zeros(L, dtype=np.int32)
+    w0 = np.ones(L, dtype=np.float32)
+    w1 = np.zeros(L, dtype=np.float32)
+    zones = []
+    start = 0  # where window i's sole ownership begins
+    for i in range(n):
+        nxt = origins[i + 1] if i + 1 < n else L
+        first[start:nxt] = i
+        if i + 1 == n:
+            break
+        end = min(origins[i] + ext, origins[i + 2] if i + 2 < n else L)
+        zones.append((nxt, end))
+        z = end - nxt
+        if z > 0:
+            beta = (np.arange(z, dtype=np.float64) + 0.5) / z
+            first[nxt:end] = i
+            w0[nxt:end] = (1.0 - beta).astype(np.float32)
+            w1[nxt:end] = beta.astype(np.float32)
+        start = end
+    c = np.arange(L)
+    o = np.asarray(origins)
+    cov_lo = np.searchsorted(o + ext, c, side="right").astype(np.int32)  # the first window with o_i + ext > c
+    cov_hi = np.searchsorted(o, c, side="right").astype(np.int32)        # the windows with o_i <= c
+    # what the kernels rely on to stay inside their buffers
+    assert origins[0] == 0 and origins[-1] == L - ext and all(0 < b - a <= ext for a, b in zip(origins, origins[1:])), origins
+    assert all(v % align == 0 for v in origins) and ((cov_lo < cov_hi) & (cov_lo >= 0) & (cov_hi <= n)).all()
+    assert ((first >= cov_lo) & (first < cov_hi)).all() and ((w1 == 0) | (first + 1 < cov_hi)).all()
+    return dict(n=n, P=ext, origins=origins, zones=zones, first=first, w0=w0, w1=w1, cov_lo=cov_lo, cov_hi=cov_hi)
+
+
+class TilePlan:
+    """The window grid of an H x W image: `y` / `x` are tile_axis_plan's results (W origins multiples of 4), rows of the window batch run
+    ((b * ny + iy) * nx + ix).  to(device) -> the same plan with the packed tables of include/idiff.h on the device:
+    ytab / xtab int32 first | cov_lo | cov_hi | origin, ywt / xwt fp32 w0 | w1."""
+
+    def __init__(self, H, W, tile, overlap):
+        if W % 4:
+            raise ValueError(f"tiled sampling: the image width {W} is not a multiple of 4")
+        self.H, self.W = int(H), int(W)
+        self.y = tile_axis_plan(self.H, tile[0], overlap[0])
+        self.x = tile_axis_plan(self.W, tile[1], overlap[1], align=4)
+        self.ny, self.nx, self.Ph, self.Pw = self.y["n"], self.x["n"], self.y["P"], self.x["P"]
+        self.ytab = self.ywt = self.xtab = self.xwt = None
+
+    @property
+    def grid(self):
+        return self.ny, self.nx, self.Ph, self.Pw
+
+    def to(self, device):
+        import numpy as np
+        for ax, it, wt in ((self.y, "ytab", "ywt"), (self.x, "xtab", "xwt")):
+            ints = np.concatenate([ax["first"], ax["cov_lo"], ax["cov_hi"], np.asarray(ax["origins"], dtype=np.int32)]).astype(np.int32)
+            setattr(self, it, torch.from_numpy(ints).to(device).contiguous())
+            setattr(self, wt, torch.from_numpy(np.concatenate([ax["w0"], ax["w1"]])).to(device).contiguous())
+        return self
+
+    def window_index(self):
+        """(yy, xx) int64 [ny*nx, Ph, Pw] on the host: the full-image coordinates of every window pixel (tests, torch-side gathers)"""
+        oy = torch.tensor(self.y["origins"]).repeat_interleave(self.nx)
+        ox = torch.tensor(self.x["origins"]).repeat(self.ny)
+        yy = (oy[:, None, None] + torch.arange(self.Ph)[None, :, None]).expand(-1, -1, self.Pw)
+        xx = (ox[:, None, None] + torch.arange(self.Pw)[None, None, :]).expand(-1, self.Ph, -1)
+        return yy, xx
+
+
 def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
     """Device tables of a schedule: coef [3, T+1] fp32 holds the jump t_k -> t_{k+1} in row t_k (k < K) and NaN in every other row;
     next_t int32 [T+1] maps t_k to t_{k+1} and every other t to -1.  The expressions and their order are _step_coeffs' with t-1
@@ -146,7 +259,8 @@ def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
 
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
-                 sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, **_ignored):
+                 sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, tile=None, tile_overlap=None,
+                 **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -172,12 +286,55 @@ class driftSDE:
         self.max_batch = _max_batch(max_batch)
         self._member_base = 1  # next unassigned member id; 0 is the stream of _randn_like and the plain chain
         self.last_members = None
+        self._tile = self._tile_o = None
+        self._tile_plans = None  # ((H, W, tile, overlap, device), TilePlan) of the last image size planned, like _jump
+        self.last_tiles = None
+        self.set_tiling(tile, tile_overlap)
 
     def set_num_samples(self, num_samples=None, max_batch=None):
         """S members per input for reverse_ddpm_ensemble (None / 1: off -- model.test() then runs reverse_ddpm); max_batch: rows per chain"""
-        self.num_samples = _num_samples(num_samples)
+        num = _num_samples(num_samples)
+        self._refuse_ensemble_of_tiles(num, getattr(self, "_tile", None))
+        self.num_samples = num
         if max_batch is not None:
             self.max_batch = _max_batch(max_batch)
+
+    @staticmethod
+    def _refuse_ensemble_of_tiles(num_samples, tile):
+        if num_samples > 1 and tile is not None:
+            raise ValueError(f"driftSDE: num_samples = {num_samples} together with tile = {list(tile)} is not supported: a posterior ensemble "
+                             "of a tiled chain is out of scope; unset one of the two")
+
+    def set_tiling(self, tile=None, overlap=None):
+        """Tiled sampling: windows of `tile` = P or [Ph, Pw] pixels (multiples of 4) that overlap by `overlap` (a multiple of 4 in
+        [0, P // 2] of either axis; None: P // 8 rounded down to a multiple of 4, per axis).  tile None: off, overlap must then be None
+        too.  reverse_ddpm takes the tiled path for an image that exceeds the window in some axis; reverse_ddpm_tiled always does."""
+        size = _tile_size(tile)
+        if size is None:
+            if overlap is not None:
+                raise ValueError(f"driftSDE: tile_overlap = {overlap!r} without tile")
+            self._tile = self._tile_o = None
+            return
+        over = (_tile_overlap(overlap, size[0]), _tile_overlap(overlap, size[1]))
+        self._refuse_ensemble_of_tiles(self.num_samples, size)
+        self._tile, self._tile_o = size, over
+
+    @property
+    def tile(self):
+        """(Ph, Pw) of tiled sampling, or None"""
+        return self._tile
+
+    @property
+    def tile_overlap(self):
+        """(Oh, Ow), or None"""
+        return self._tile_o
+
+    def _tile_plan(self, H, W, device):
+        """the device TilePlan of an H x W image under the current tiling, built once per (H, W, tile, overlap)"""
+        key = (int(H), int(W), self._tile, self._tile_o, str(device))
+        if self._tile_plans is None or self._tile_plans[0] != key:
+            self._tile_plans = (key, TilePlan(H, W, self._tile, self._tile_o).to(device))
+        return self._tile_plans[1]
 
     def set_solver_order(self, order=None):
         """1 (or None): the first-order jump; 2: the second-order multistep jump (reverse_ddpm only, like set_sample_steps)"""
@@ -412,6 +569,51 @@ class driftSDE:
             """'graph' when the loop replays a captured HIP graph, 'eager' otherwise (reported by bench.py)"""
             return "graph" if self.graph else "eager"
 
+    class TiledStepper(Stepper):
+        """Stepper for tiled sampling: x / cond are the full image, `plan` its device TilePlan; names and image_context come in per window
+        row.  A step runs predict on chunks of at most sde.max_batch window rows, lands the chunks' predictions in the persistent r_tiles /
+        e_tiles (one chunk: the nets' outputs are used as they are), then the fused tiled step on the full image -- which also rewrites
+        the window inputs x_tiles / xa_tiles -- and the state advance over all window rows.  Warm step, capture, replay and the Philox
+        accounting (nper = the FULL image's float4 count, as the plain chain's) are Stepper's."""
+
+        def __init__(self, sde, x, cond, plan, names, text_encoder, image_context, **kw):
+            super().__init__(sde, x, cond, names, text_encoder, image_context, **kw)
+            if self.members is not None:
+                raise ValueError("TiledStepper: member streams are not supported")
+            self.plan = plan
+            R = x.shape[0] * plan.ny * plan.nx
+            if len(names) != R or (image_context is not None and image_context.shape[0] != R):
+                raise ValueError(f"TiledStepper: names / image_context must come per window row ({R})")
+            self.tdev = torch.full((R,), float(self.state[0].item()), dtype=torch.float32, device=x.device)
+            self.cond_tiles = ops.tile_gather(cond, plan)
+            self.x_tiles = ops.tile_gather(x, plan)
+            self.xa_tiles = ops.tile_gather(self.xa, plan)
+            self.chunks = []
+            for r0 in range(0, R, sde.max_batch):
+                r1 = min(r0 + sde.max_batch, R)
+                self.chunks.append((r0, r1, list(names[r0:r1]), None if image_context is None else image_context[r0:r1].contiguous()))
+            if len(self.chunks) > 1:
+                self.r_tiles, self.e_tiles = torch.empty_like(self.x_tiles), torch.empty_like(self.x_tiles)
+
+        def _body(self):
+            sde = self.sde
+            for r0, r1, names, ctx in self.chunks:
+                r_hat, e_hat = sde.predict(self.xa_tiles[r0:r1], self.x_tiles[r0:r1], self.cond_tiles[r0:r1], self.tdev[r0:r1], names,
+                                           self.text_encoder, ctx)
+                if len(self.chunks) == 1:
+                    r_tiles, e_tiles = r_hat, e_hat
+                else:  # 1*r + 0*r: a copy by a library launch, into the rows the step reads
+                    r_tiles, e_tiles = self.r_tiles, self.e_tiles
+                    ops.axpby(r_hat, r_hat, 1.0, 0.0, out=r_tiles[r0:r1])
+                    ops.axpby(e_hat, e_hat, 1.0, 0.0, out=e_tiles[r0:r1])
+            hist = (self.r_prev, self.e_prev) if self.order == 2 else (None, None)
+            ops.drift_reverse_step_tiled_dev(self.x, r_tiles, e_tiles, hist[0], hist[1], self.noises, self.cond, self.x_tiles, self.xa_tiles,
+                                             self.plan, self.coef, self.state, sde.seed, self.nper, self.off_base)
+            if self.next_t is None:
+                ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
+            else:
+                ops.step_state_advance_table(self.state, self.tdev, self.next_t, self.t_first, self.t_stop)
+
     def _chain_plan(self, reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm"):
         """-> (schedule or None, steps, solver order) of a reverse chain down to T_stop, after the option checks"""
         if optimize_type not in ("inputRes", "predict_noise", ""):
@@ -441,12 +643,16 @@ class driftSDE:
         With a few-step schedule (sample_T / sample_timesteps) the loop runs K = len(timesteps) - 1 jumps t_k -> t_{k+1}, noises is
         [K, ...] indexed by step and T_stop must be 0 or a schedule point.  self.last_steps: the steps this call ran.
         solver_order = 2 always runs the schedule path (T, T-1, ..., 0 when no schedule is set).  self.last_solver_order: the order that ran."""
+        if self._tile is not None and cond.dim() == 4 and (cond.shape[2] > self._tile[0] or cond.shape[3] > self._tile[1]):
+            return self.reverse_ddpm_tiled(cond, names, text_encoder, reverse_type=reverse_type, optimize_type=optimize_type,
+                                           image_context=image_context, x_T=x_T, noises=noises, T_stop=T_stop)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop)
         cond = cond.contiguous()
         B = cond.shape[0]
         if x_T is None:
             x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
         x = x_T.contiguous().clone()
+        self.last_tiles = None
         if sched is None:
             stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
         else:
@@ -456,6 +662,40 @@ class driftSDE:
         self.last_mode = stepper.mode  # 'graph' | 'eager': how the loop of this call ran
         self.last_steps = nsteps
         self.last_solver_order = order
+        return out
+
+    @torch.no_grad()
+    def reverse_ddpm_tiled(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None, x_T=None,
+                           noises=None, T_stop=0):
+        """reverse_ddpm on the window grid of set_tiling, whatever the image size (a single window included).  cond, x_T, noises and the
+        result are full images ([B, C, H, W], W a multiple of 4); the schedule, solver order, eta, T_stop, the x_T draw and the Philox
+        accounting are reverse_ddpm's for that image, and with on-device noise every pixel gets the z the plain chain would give it.
+        `names` and `image_context` are repeated per window: the whole image's embedding serves each of its windows.  The window rows
+        run through the nets in chunks of at most max_batch.  self.last_tiles: the grid that ran, (ny, nx, Ph, Pw)."""
+        if self._tile is None:
+            raise ValueError("reverse_ddpm_tiled: no tiling is set (set_tiling / the tile option)")
+        self._refuse_ensemble_of_tiles(self.num_samples, self._tile)
+        sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_tiled")
+        cond = cond.contiguous()
+        if cond.dim() != 4:
+            raise ValueError(f"reverse_ddpm_tiled: cond must be [B, C, H, W], got {tuple(cond.shape)}")
+        B, _, H, W = cond.shape
+        if W % 4:
+            raise ValueError(f"reverse_ddpm_tiled: the image width {W} is not a multiple of 4")
+        plan = self._tile_plan(H, W, cond.device)
+        if x_T is None:
+            x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
+        x = x_T.contiguous().clone()
+        nwin = plan.ny * plan.nx
+        names_rep = [n for n in names for _ in range(nwin)]
+        ctx_rep = None if image_context is None else image_context.repeat_interleave(nwin, dim=0)
+        stepper = driftSDE.TiledStepper(self, x, cond, plan, names_rep, text_encoder, ctx_rep, noises=noises, t_stop=T_stop, timesteps=sched,
+                                        solver_order=order)
+        out = stepper.run(nsteps)
+        self.last_mode = stepper.mode
+        self.last_steps = nsteps
+        self.last_solver_order = order
+        self.last_tiles = plan.grid
         return out
 
     def _assign_members(self, B, S, members):
@@ -479,6 +719,7 @@ class driftSDE:
         own (schedule, solver_order, warm step, capture and T_stop as in reverse_ddpm), and are reduced on the device.  `noises`
         ([steps, B*S, ...]) injects the per-step draws.  self.last_members: the ids used, [B, S]."""
         S = self.num_samples if num_samples is None else _num_samples(num_samples)
+        self._refuse_ensemble_of_tiles(S, self._tile)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_ensemble")
         cond = cond.contiguous()
         B = cond.shape[0]

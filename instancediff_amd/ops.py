@@ -868,6 +868,55 @@ def ensemble_stats(x):
     return mean, std
 
 
+# ---- tiled sampling (include/idiff.h; the plan is models/SDEs/driftSDE.py's TilePlan, moved to the device by plan.to(device)) ----
+def _tile_args(plan, full, name):
+    """(B, C, H, W, ny, nx, Ph, Pw) of a full image under a device plan, after the shape checks"""
+    if full.dim() != 4 or tuple(full.shape[2:]) != (plan.H, plan.W):
+        raise _lib.IdiffError(f"{name}: the image must be [B, C, {plan.H}, {plan.W}] for this plan, got {tuple(full.shape)}")
+    for t, dt in ((plan.ytab, torch.int32), (plan.xtab, torch.int32), (plan.ywt, torch.float32), (plan.xwt, torch.float32)):
+        _c(t, "plan table", dt)
+    return (full.shape[0], full.shape[1], plan.H, plan.W, plan.ny, plan.nx, plan.Ph, plan.Pw)
+
+
+def tile_gather(full, plan, out=None):
+    """full [B, C, H, W] -> windows [B*ny*nx, C, Ph, Pw], row (b*ny + iy)*nx + ix = full[b, :, oy[iy]:+Ph, ox[ix]:+Pw]"""
+    lib = _lib.load()
+    _c(full, "full")
+    dims = _tile_args(plan, full, "tile_gather")
+    B, Cc = dims[:2]
+    shape = (B * plan.ny * plan.nx, Cc, plan.Ph, plan.Pw)
+    if out is None:
+        out = torch.empty(shape, device=full.device, dtype=torch.float32)
+    _c(out, "out")
+    assert tuple(out.shape) == shape, (tuple(out.shape), shape)
+    check(lib.idiff_tile_gather(_p(full), _p(out), *dims, C.c_void_p(plan.ytab.data_ptr()), C.c_void_p(plan.xtab.data_ptr()), _stream()),
+          "tile_gather")
+    return out
+
+
+def drift_reverse_step_tiled_dev(x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, plan, coef, state, seed, nper,
+                                 offset_base=0):
+    """the step of a tiled chain, in place on the full image x [B, C, H, W]: blends the window predictions r_tiles / e_tiles
+    [B*ny*nx, C, Ph, Pw], updates x as drift_reverse_step_dev (coef [3, T+1], r_prev = e_prev = None) or drift_reverse_step2_dev (coef
+    [5, T+1], full-image history) does, and scatters x and x - cond into x_tiles / xa_tiles"""
+    lib = _lib.load()
+    _c(x, "x"), _c(r_tiles, "r_tiles"), _c(e_tiles, "e_tiles"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
+    _c(x_tiles, "x_tiles"), _c(xa_tiles, "xa_tiles"), _c(coef, "coef"), _c(state, "state", torch.int32)
+    dims = _tile_args(plan, x, "drift_reverse_step_tiled_dev")
+    nt = dims[0] * plan.ny * plan.nx * dims[1] * plan.Ph * plan.Pw
+    assert state.numel() == 3 and coef.dim() == 2 and coef.shape[0] in (3, 5)
+    for t in (r_tiles, e_tiles, x_tiles, xa_tiles):
+        assert t.numel() == nt, (t.numel(), nt)
+    for t in (r_prev, e_prev, cond):
+        assert t is None or t.numel() == x.numel()
+    assert z_base is None or (z_base.numel() % x.numel() == 0 and z_base.numel() >= x.numel())
+    check(lib.idiff_drift_reverse_step_tiled_dev(_p(x), _p(r_tiles), _p(e_tiles), _p(r_prev), _p(e_prev), _p(z_base), _p(cond), _p(x_tiles),
+                                                 _p(xa_tiles), *dims, C.c_void_p(plan.ytab.data_ptr()), _p(plan.ywt),
+                                                 C.c_void_p(plan.xtab.data_ptr()), _p(plan.xwt), _p(coef), coef.shape[0], coef.shape[1],
+                                                 C.c_void_p(state.data_ptr()), seed, nper, offset_base, _stream()),
+          "drift_reverse_step_tiled_dev")
+
+
 def step_state_advance(state, tdev, T, t_stop=0):
     lib = _lib.load()
     _c(tdev, "tdev")

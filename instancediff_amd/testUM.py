@@ -6,7 +6,9 @@
 Reads `test: {iter, pth_dir, use_ema, which_model, which_sde, result_root}` (testUM.py:71-100), restores every
 image of the test sets with `model.test()` (timed like :141-144), computes RMSE / PSNR / SSIM per image on the
 device (:151-164) and writes the LQ|pred|GT `.raw` triptychs (:170-173).  With `--num-samples S` (driftSDE) each image is restored as
-an S-member posterior ensemble: the metrics and the triptych are the mean's, `PSNR_member` / `STD` and a `<i>_std_WxHx1.raw` map are added.  With `--random-init` the checkpoint load
+an S-member posterior ensemble: the metrics and the triptych are the mean's, `PSNR_member` / `STD` and a `<i>_std_WxHx1.raw` map are added.
+With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
+full-resolution chain.  With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
@@ -37,7 +39,13 @@ def main(argv=None):
                              "the per-pixel standard deviation is written next to it (overrides the YAML)")
     parser.add_argument("--max-batch", type=int, default=None, metavar="M",
                         help="driftSDE max_batch: rows per chain of an ensemble (overrides the YAML)")
+    parser.add_argument("--tile", type=int, nargs="+", default=None, metavar="P",
+                        help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
+    parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
+                        help="driftSDE tile_overlap: pixels shared by adjacent windows (default tile // 8; overrides the YAML)")
     args = parser.parse_args(argv)
+    if args.tile is not None and len(args.tile) > 2:
+        parser.error("--tile takes one size P or two, Ph Pw")
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
     rank, world, local = parallel.init_distributed()
@@ -58,6 +66,10 @@ def main(argv=None):
         sde_opt['num_samples'] = args.num_samples
     if args.max_batch is not None:
         sde_opt['max_batch'] = args.max_batch
+    if args.tile is not None:
+        sde_opt['tile'] = args.tile[0] if len(args.tile) == 1 else list(args.tile)
+    if args.tile_overlap is not None:
+        sde_opt['tile_overlap'] = args.tile_overlap
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
@@ -114,7 +126,8 @@ def main(argv=None):
     if times:
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
-              + (f", {S} samples per image" if S > 1 else ""))
+              + (f", {S} samples per image" if S > 1 else "")
+              + ("" if getattr(sde, 'last_tiles', None) is None else ", {}x{} windows of {}x{}".format(*sde.last_tiles)))
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return results
