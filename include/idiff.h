@@ -504,6 +504,23 @@ int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat, const flo
  * S <= 16 and reads them a second time above that (IDIFF_ENSEMBLE_REREAD=1 in the environment forces the second form; the bits are the
  * same).  The result of image b does not depend on B. */
 int idiff_ensemble_stats(const float* x, float* mean, float* std_out, int B, int S, int64_t n_s, idiff_stream_t stream);
+/* Per-pixel order statistics of an ensemble: x [B][S][n_s] -> out [B][nk][n_s], plane i = per pixel the ks_host[i]-th smallest
+ * (0-based) of the pixel's S values.  1 <= nk <= 8; ks_host: nk host ints in [0, S), any order, duplicates allowed, passed to the kernel by
+ * value (no device table).  Values are selected, never rounded: the result equals a sort of the S values, by value (which of two equal
+ * values -- a signed zero -- is returned is unspecified).  If any of a pixel's S values is NaN, every plane is NaN at that pixel; +-inf
+ * sort as values.  algo: 0 = auto, 1 = network form (S <= 16: the S float4 of a thread in registers, padded with +inf to 2 / 4 / 8 / 16, a
+ * fixed odd-even merge sort network of v_min_f32 / v_max_f32), 2 = rank form (any S: rank_s = #{j : x_j < x_s} + #{j < s : x_j == x_s},
+ * the candidate of rank ks[i] is stored; O(S^2) compares on re-read values).  Auto takes the network for S <= 16.  Both forms give the same
+ * values.  n_s % 4 == 0, operands 16-byte aligned, B <= 65535, out != x; a refused call leaves the buffers untouched. */
+int idiff_ensemble_order_stats(const float* x, float* out, int B, int S, int64_t n_s, const int32_t* ks_host, int nk, int algo,
+                               idiff_stream_t stream);
+/* Coverage of an interval map: lo, hi, target [B][n_s] -> counts [B][3] = {target < lo, lo <= target <= hi, target > hi} as exact integers.
+ * A pixel where lo, hi or target is NaN counts nowhere (the three need not sum to n_s); where lo > hi nothing is inside.  Per-block partial
+ * counts go to ws (idiff_interval_coverage_ws_ints(B, n_s) int32), a second launch adds them: no atomics, no float sums.
+ * n_s % 4 == 0, n_s < 2^31, operands 16-byte aligned, B <= 65535. */
+int idiff_interval_coverage(const float* lo, const float* hi, const float* target, int32_t* counts, int32_t* ws, int B, int64_t n_s,
+                            idiff_stream_t stream);
+int64_t idiff_interval_coverage_ws_ints(int B, int64_t n_s);
 /* ---- tiled sampling (driftSDE tile / tile_overlap) ----
  * The chain's state is one full-resolution image [B][C][H][W]; the nets see it as a batch of ny*nx windows of Ph x Pw per image, window
  * row ((b*ny + iy)*nx + ix), each [C][Ph][Pw] contiguous.  W, Pw and the W origins are multiples of 4; all operands 16-byte aligned.

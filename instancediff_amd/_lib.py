@@ -130,6 +130,9 @@ SIGNATURES = {
     "idiff_ensemble_init": (I, [P, P, P, P, I, I, I64, P, F, U64, c_stream]),
     "idiff_drift_reverse_step_members_dev": (I, [P, P, P, P, P, P, P, P, I, I64, P, I, I, P, P, U64, c_stream]),
     "idiff_ensemble_stats": (I, [P, P, P, I, I, I64, c_stream]),
+    "idiff_ensemble_order_stats": (I, [P, P, I, I, I64, C.POINTER(C.c_int32), I, I, c_stream]),
+    "idiff_interval_coverage": (I, [P, P, P, P, P, I, I64, c_stream]),
+    "idiff_interval_coverage_ws_ints": (I64, [I, I64]),
     "idiff_tile_gather": (I, [P, P, I, I, I, I, I, I, I, I, P, P, c_stream]),
     "idiff_drift_reverse_step_tiled_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, U64, U64, U64, c_stream]),
     "idiff_step_state_advance": (I, [P, P, I, I, I, c_stream]),

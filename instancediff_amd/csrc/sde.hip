@@ -6,6 +6,7 @@
 
 #include <cstdlib>
 #include <initializer_list>
+#include <utility>
 
 // hipcc defaults to -ffp-contract=fast-honor-pragmas: without this the separate mul/sub below fuse to FMAs
 // and the result differs from the reference's op-by-op fp32 arithmetic in the last bit.
@@ -998,5 +999,285 @@ extern "C" int idiff_ensemble_stats(const float* x, float* mean, float* std_out,
     else
         hipLaunchKernelGGL(ensemble_stats_kernel<false>, rows_grid(Q, B), dim3(256), 0, (hipStream_t)stream, x, mean, std_out, S, Q);
     IDIFF_CHECK_LAUNCH("ensemble_stats");
+    return IDIFF_OK;
+}
+
+// ---- posterior ensembles: per-pixel order statistics and interval coverage ----
+namespace {
+
+constexpr int ORD_MAX_K = 8;     // output planes per launch
+constexpr int ORD_NET_MAX = 16;  // the network form keeps a thread's S float4 in registers up to here (= ENS_REG)
+struct OrderKs {
+    int k[ORD_MAX_K];
+};
+
+// Batcher's odd-even merge sort on n = 2^m wires as a fixed list of compare-exchanges (a, b), a < b, evaluated at compile time:
+// comparator idx of the list, or {-1, idx's excess over the list} past its end.  n = 2, 4, 8, 16 -> 1, 5, 19, 63 comparators.
+struct CePair {
+    int a, b;
+};
+constexpr CePair oem_pair(int n, int idx) {
+    int seen = 0;
+    for (int p = 1; p < n; p *= 2)
+        for (int k = p; k >= 1; k /= 2)
+            for (int j = k % p; j + k < n; j += 2 * k)
+                for (int i = 0; i < k && i + j + k < n; ++i)
+                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+                        if (seen == idx) return CePair{i + j, i + j + k};
+                        ++seen;
+                    }
+    return CePair{-1, seen};
+}
+constexpr int oem_count(int n) { return oem_pair(n, 1 << 30).b; }
+static_assert(oem_count(1) == 0 && oem_count(2) == 1 && oem_count(4) == 5 && oem_count(8) == 19 && oem_count(16) == 63, "odd-even merge sort");
+
+// v_min_f32 / v_max_f32 per lane: both return one of their operands' values, so the network permutes values and rounds nothing
+template <int NP, int I>
+__device__ __forceinline__ void oem_exchange(floatx4 (&val)[NP]) {
+    constexpr int a = oem_pair(NP, I).a, b = oem_pair(NP, I).b;
+    static_assert(a >= 0 && a < b && b < NP, "comparator out of range");
+    const floatx4 lo = val[a], hi = val[b];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        val[a][e] = fminf(lo[e], hi[e]);
+        val[b][e] = fmaxf(lo[e], hi[e]);
+    }
+}
+template <int NP, int... I>
+__device__ __forceinline__ void oem_sort(floatx4 (&val)[NP], std::integer_sequence<int, I...>) {
+    (oem_exchange<NP, I>(val), ...);
+}
+
+// val[k] for a wave-uniform k in [0, NP): a uniform branch to one constant-index read, so val[] is never indexed at run time (no
+// scratch) and the choice costs no per-lane select
+template <int NP>
+__device__ __forceinline__ floatx4 order_pick(const floatx4 (&val)[NP], int k) {
+    floatx4 o = val[0];
+#define ORD_CASE(s)                       \
+    case s:                               \
+        if constexpr (s < NP) o = val[s]; \
+        break;
+    switch (k) {
+        ORD_CASE(1) ORD_CASE(2) ORD_CASE(3) ORD_CASE(4) ORD_CASE(5) ORD_CASE(6) ORD_CASE(7) ORD_CASE(8)
+        ORD_CASE(9) ORD_CASE(10) ORD_CASE(11) ORD_CASE(12) ORD_CASE(13) ORD_CASE(14) ORD_CASE(15)
+        default:
+            break;
+    }
+#undef ORD_CASE
+    return o;
+}
+static_assert(ORD_NET_MAX == 16, "order_pick lists 16 cases");
+
+// Network form, S <= NP <= 16: a thread loads its S float4 into registers (padded with +inf to NP), sorts them ascending through the
+// fixed network and stores registers ks[0..nk), each picked by order_pick, so val[] stays in VGPRs.  A NaN among the S values of a pixel makes every plane NaN there.
+template <int NP>
+__global__ __launch_bounds__(256) void ensemble_order_net_kernel(const float* __restrict__ x, float* __restrict__ out, int S, int nk, long long Q,
+                                                                 OrderKs ks) {
+    const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (long long)blockIdx.y * S * Q;
+    floatx4* os = reinterpret_cast<floatx4*>(out) + (long long)blockIdx.y * nk * Q;
+    const float inf = __builtin_huge_valf(), qnan = __builtin_nanf("");
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        floatx4 val[NP];
+        bool bad[4] = {false, false, false, false};
+#pragma unroll
+        for (int s = 0; s < NP; ++s) {
+            if (s < S) {
+                val[s] = xs[(long long)s * Q + v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bad[e] |= val[s][e] != val[s][e];
+            } else {
+                val[s] = floatx4{inf, inf, inf, inf};
+            }
+        }
+        oem_sort<NP>(val, std::make_integer_sequence<int, oem_count(NP)>{});
+#pragma unroll
+        for (int i = 0; i < ORD_MAX_K; ++i)
+            if (i < nk) {
+                floatx4 o = order_pick<NP>(val, ks.k[i]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = bad[e] ? qnan : o[e];
+                os[(long long)i * Q + v] = o;
+            }
+    }
+}
+
+// Rank form, any S: candidate s has rank #{j : x_j < x_s} + #{j < s : x_j == x_s}, a permutation of 0..S-1 when no value is NaN, and the
+// candidate of rank ks[i] is plane i's value.  Candidates are taken ORD_CH at a time in registers, so the S values are read S / ORD_CH
+// times (the re-reads hit L2); members before the chunk count with <=, members after it with <, members inside it by their index.  The
+// nk outputs collect in registers and are stored once per pixel, with the network form's NaN rule.
+constexpr int ORD_CH = 4;
+__global__ __launch_bounds__(256) void ensemble_order_rank_kernel(const float* __restrict__ x, float* __restrict__ out, int S, int nk, long long Q,
+                                                                  OrderKs ks) {
+    const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (long long)blockIdx.y * S * Q;
+    floatx4* os = reinterpret_cast<floatx4*>(out) + (long long)blockIdx.y * nk * Q;
+    const float qnan = __builtin_nanf("");
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        floatx4 o[ORD_MAX_K];
+        bool bad[4] = {false, false, false, false};
+#pragma unroll
+        for (int i = 0; i < ORD_MAX_K; ++i) o[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+        for (int s0 = 0; s0 < S; s0 += ORD_CH) {
+            floatx4 cand[ORD_CH];
+            int rank[ORD_CH][4];
+#pragma unroll
+            for (int c = 0; c < ORD_CH; ++c) {
+                const int s = s0 + c < S ? s0 + c : S - 1;  // past the end: a copy of the last member, never selected
+                cand[c] = xs[(long long)s * Q + v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    bad[e] |= cand[c][e] != cand[c][e];
+                    rank[c][e] = 0;
+                }
+            }
+            for (int j = 0; j < s0; ++j) {
+                const floatx4 xj = xs[(long long)j * Q + v];
+#pragma unroll
+                for (int c = 0; c < ORD_CH; ++c)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) rank[c][e] += xj[e] <= cand[c][e] ? 1 : 0;
+            }
+#pragma unroll
+            for (int jj = 0; jj < ORD_CH; ++jj)
+                if (s0 + jj < S) {
+#pragma unroll
+                    for (int c = 0; c < ORD_CH; ++c) {
+                        if (c == jj) continue;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) rank[c][e] += (jj < c ? cand[jj][e] <= cand[c][e] : cand[jj][e] < cand[c][e]) ? 1 : 0;
+                    }
+                }
+            for (int j = s0 + ORD_CH; j < S; ++j) {
+                const floatx4 xj = xs[(long long)j * Q + v];
+#pragma unroll
+                for (int c = 0; c < ORD_CH; ++c)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) rank[c][e] += xj[e] < cand[c][e] ? 1 : 0;
+            }
+#pragma unroll
+            for (int c = 0; c < ORD_CH; ++c)
+                if (s0 + c < S) {
+#pragma unroll
+                    for (int i = 0; i < ORD_MAX_K; ++i)
+                        if (i < nk) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[i][e] = rank[c][e] == ks.k[i] ? cand[c][e] : o[i][e];
+                        }
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < ORD_MAX_K; ++i)
+            if (i < nk) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[i][e] = bad[e] ? qnan : o[i][e];
+                os[(long long)i * Q + v] = o[i];
+            }
+    }
+}
+
+// Interval coverage: integer counts {target < lo, lo <= target <= hi, target > hi} per image; a pixel where any of the three is NaN
+// counts nowhere.  COV_PARTS blocks per image write partial counts, a second launch adds them: integers only, no atomics.
+constexpr int COV_PARTS = 64;
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ __launch_bounds__(256) void interval_coverage_partial_kernel(const float* __restrict__ lo, const float* __restrict__ hi,
+                                                                        const float* __restrict__ tgt, int32_t* __restrict__ part, long long Q) {
+    __shared__ int red[3][4];
+    const long long row = (long long)blockIdx.y * Q;
+    const floatx4* l4 = reinterpret_cast<const floatx4*>(lo) + row;
+    const floatx4* h4 = reinterpret_cast<const floatx4*>(hi) + row;
+    const floatx4* t4 = reinterpret_cast<const floatx4*>(tgt) + row;
+    int below = 0, inside = 0, above = 0;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        const floatx4 lv = l4[v], hv = h4[v], tv = t4[v];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool ok = lv[e] == lv[e] && hv[e] == hv[e];  // a NaN target fails every comparison below by itself
+            below += (ok && tv[e] < lv[e]) ? 1 : 0;
+            inside += (ok && tv[e] >= lv[e] && tv[e] <= hv[e]) ? 1 : 0;
+            above += (ok && tv[e] > hv[e]) ? 1 : 0;
+        }
+    }
+    below = wave_sum_int(below);
+    inside = wave_sum_int(inside);
+    above = wave_sum_int(above);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = below;
+        red[1][threadIdx.x >> 6] = inside;
+        red[2][threadIdx.x >> 6] = above;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        part[((long long)blockIdx.y * COV_PARTS + blockIdx.x) * 3 + threadIdx.x] =
+            (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ void interval_coverage_final_kernel(const int32_t* __restrict__ part, int32_t* __restrict__ counts, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (b, which)
+    if (i >= B * 3) return;
+    const int b = i / 3, w = i - b * 3;
+    int acc = 0;
+    for (int p = 0; p < COV_PARTS; ++p) acc += part[((long long)b * COV_PARTS + p) * 3 + w];
+    counts[i] = acc;
+}
+
+template <int NP>
+void launch_order_net(const float* x, float* out, int B, int S, int nk, long long Q, const OrderKs& ks, hipStream_t st) {
+    hipLaunchKernelGGL(ensemble_order_net_kernel<NP>, rows_grid(Q, B), dim3(256), 0, st, x, out, S, nk, Q, ks);
+}
+
+}  // namespace
+
+extern "C" int idiff_ensemble_order_stats(const float* x, float* out, int B, int S, int64_t n_s, const int32_t* ks_host, int nk, int algo,
+                                          idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(x && out && ks_host && B > 0 && B <= 65535 && S > 0 && n_s > 0, "ensemble_order_stats: bad args");
+    IDIFF_CHECK_ARG(nk >= 1 && nk <= ORD_MAX_K, "ensemble_order_stats: nk = %d is outside [1, %d]", nk, ORD_MAX_K);
+    IDIFF_CHECK_ARG(algo >= 0 && algo <= 2, "ensemble_order_stats: algo must be 0 (auto), 1 (network) or 2 (rank), got %d", algo);
+    IDIFF_CHECK_ARG(algo != 1 || S <= ORD_NET_MAX, "ensemble_order_stats: the network form holds at most %d members, got S = %d", ORD_NET_MAX, S);
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "ensemble_order_stats: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({x, out}), "ensemble_order_stats: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(out != x, "ensemble_order_stats: out must not be x");
+    OrderKs ks;
+    for (int i = 0; i < ORD_MAX_K; ++i) {
+        ks.k[i] = i < nk ? ks_host[i] : 0;
+        IDIFF_CHECK_ARG(ks.k[i] >= 0 && ks.k[i] < S, "ensemble_order_stats: ks[%d] = %d is outside [0, S = %d)", i, ks.k[i], S);
+    }
+    const long long Q = n_s / 4;
+    hipStream_t st = (hipStream_t)stream;
+    if (algo == 2 || S > ORD_NET_MAX)
+        hipLaunchKernelGGL(ensemble_order_rank_kernel, rows_grid(Q, B), dim3(256), 0, st, x, out, S, nk, Q, ks);
+    else if (S == 1)
+        launch_order_net<1>(x, out, B, S, nk, Q, ks, st);
+    else if (S == 2)
+        launch_order_net<2>(x, out, B, S, nk, Q, ks, st);
+    else if (S <= 4)
+        launch_order_net<4>(x, out, B, S, nk, Q, ks, st);
+    else if (S <= 8)
+        launch_order_net<8>(x, out, B, S, nk, Q, ks, st);
+    else
+        launch_order_net<16>(x, out, B, S, nk, Q, ks, st);
+    IDIFF_CHECK_LAUNCH("ensemble_order_stats");
+    return IDIFF_OK;
+}
+
+extern "C" int64_t idiff_interval_coverage_ws_ints(int B, int64_t n_s) {
+    (void)n_s;
+    return B > 0 ? (int64_t)B * COV_PARTS * 3 : 0;
+}
+
+extern "C" int idiff_interval_coverage(const float* lo, const float* hi, const float* target, int32_t* counts, int32_t* ws, int B, int64_t n_s,
+                                       idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(lo && hi && target && counts && ws && B > 0 && B <= 65535 && n_s > 0 && n_s <= 0x7fffffffLL, "interval_coverage: bad args");
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "interval_coverage: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({lo, hi, target}), "interval_coverage: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(counts != ws, "interval_coverage: counts must not be ws");
+    const long long Q = n_s / 4;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(interval_coverage_partial_kernel, dim3(COV_PARTS, (unsigned)B), dim3(256), 0, st, lo, hi, target, ws, Q);
+    IDIFF_CHECK_LAUNCH("interval_coverage_partial");
+    hipLaunchKernelGGL(interval_coverage_final_kernel, dim3((B * 3 + 63) / 64), dim3(64), 0, st, (const int32_t*)ws, counts, B);
+    IDIFF_CHECK_LAUNCH("interval_coverage_final");
     return IDIFF_OK;
 }

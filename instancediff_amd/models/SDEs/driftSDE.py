@@ -29,7 +29,12 @@ Tiled sampling (`tile` / `tile_overlap`): an image larger than th
 overlapping windows.  The state stays ONE full-resolution image: every step blends the windows' two predictions into full-image R_hat and
 eps_hat, updates and draws the noise once per pixel on the full image (the plain chain's Philox counters, whatever the tiling), and cuts the
 next step's window inputs out again -- one fused kernel per step beside the nets.
+
+Credible intervals (`interval: L`): with it reverse_ddpm_ensemble also selects, per pixel, the order statistics of the S
+members that bracket the central level-L interval and the median (one launch, values selected and never rounded) into
+self.last_order_stats.  order_stat_indices states which order statistics those are and the coverage they nominally give.
 """
+import fractions
 import math
 import numbers
 import os
@@ -112,6 +117,30 @@ def _num_samples(num):
     if not isinstance(num, numbers.Integral) or isinstance(num, bool) or num < 1:
         raise ValueError(f"driftSDE: num_samples must be an int >= 1 (or None: off), got {num!r}")
     return int(num)
+
+
+def _interval(level):
+    """credible level of the ensemble's interval maps as a float in (0, 1) (None: off); bools, ints and strings are refused like
+    solver_order's"""
+    if level is None:
+        return None
+    if not isinstance(level, float) or not 0.0 < level < 1.0:
+        raise ValueError(f"driftSDE: interval must be a float in (0, 1) (or None: off), got {level!r}")
+    return level
+
+
+def order_stat_indices(S, level):
+    """The order statistics (0-based, of S members sorted ascending) behind a central interval of credible level L, in exact rational
+    arithmetic on the decimal the caller wrote (Fraction(str(level)): 0.9 is 9/10, not the double next to it):
+        k_lo = floor((1 - L) / 2 * (S - 1)),  k_hi = S - 1 - k_lo      the interval [x_(k_lo), x_(k_hi)]
+        k_m0 = (S - 1) // 2,  k_m1 = S // 2                            the median, 0.5 * (x_(k_m0) + x_(k_m1))
+        nominal = (k_hi - k_lo) / (S + 1)                              the coverage S exchangeable draws give that pair
+    With few members nominal lies below L (S = 4: min / max, 0.6)."""
+    S = _num_samples(S)
+    L = fractions.Fraction(str(_interval(level)))
+    k_lo = math.floor((1 - L) / 2 * (S - 1))
+    k_hi = S - 1 - k_lo
+    return dict(k_lo=k_lo, k_hi=k_hi, k_m0=(S - 1) // 2, k_m1=S // 2, nominal=(k_hi - k_lo) / (S + 1))
 
 
 def _max_batch(rows):
@@ -260,7 +289,7 @@ def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
                  sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, tile=None, tile_overlap=None,
-                 **_ignored):
+                 interval=None, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -290,6 +319,13 @@ class driftSDE:
         self._tile_plans = None  # ((H, W, tile, overlap, device), TilePlan) of the last image size planned, like _jump
         self.last_tiles = None
         self.set_tiling(tile, tile_overlap)
+        self.last_order_stats = None
+        self.set_interval(interval)
+
+    def set_interval(self, level=None):
+        """credible level L in (0, 1) of the interval maps reverse_ddpm_ensemble leaves in last_order_stats (None: off).  Only
+        reverse_ddpm_ensemble reads it; with num_samples = 1 the plain chain runs and it does nothing."""
+        self.interval = _interval(level)
 
     def set_num_samples(self, num_samples=None, max_batch=None):
         """S members per input for reverse_ddpm_ensemble (None / 1: off -- model.test() then runs reverse_ddpm); max_batch: rows per chain"""
@@ -717,7 +753,10 @@ class driftSDE:
         Row b*S + s is member m(b, s), whose x_T draw and per-step z come from its own Philox stream (include/idiff.h): its image is the
         same in any batch, chunking or call order.  The B*S rows run in chunks of at most max_batch rows, each through a Stepper of its
         own (schedule, solver_order, warm step, capture and T_stop as in reverse_ddpm), and are reduced on the device.  `noises`
-        ([steps, B*S, ...]) injects the per-step draws.  self.last_members: the ids used, [B, S]."""
+        ([steps, B*S, ...]) injects the per-step draws.  self.last_members: the ids used, [B, S].
+        With `interval` = L set, self.last_order_stats = dict(lo, hi, median [B, ...], level, nominal, ks): the order statistics of
+        order_stat_indices(S, L) as contiguous maps, from one ops.ensemble_order_stats launch over the samples (plus one axpby for the
+        median of an even S, and for B > 1 one ops.gather_channel per map); None without it."""
         S = self.num_samples if num_samples is None else _num_samples(num_samples)
         self._refuse_ensemble_of_tiles(S, self._tile)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_ensemble")
@@ -746,4 +785,27 @@ class driftSDE:
         self.last_members = torch.tensor(ids, dtype=torch.int64).view(B, S)
         samples = x.view((B, S) + tuple(cond.shape[1:]))
         mean, std = ops.ensemble_stats(samples)
+        self.last_order_stats = None if self.interval is None else self._order_stats(samples, self.interval)
         return (mean, std, samples) if return_samples else (mean, std)
+
+    @staticmethod
+    def _order_stats(samples, level):
+        """lo / hi / median maps of samples [B, S, ...] at credible level `level`, each a contiguous [B, ...]: planes k_lo, k_hi, k_m0,
+        k_m1 of ONE selection launch over the samples.  With B = 1 the maps are that result's planes themselves; with B > 1 a plane
+        is strided over the batch and is copied out by ops.gather_channel (a library launch per map, exact).  An even S's median is
+        0.5*x_(k_m0) + 0.5*x_(k_m1) (ops.axpby: both products exact, one rounded add), an odd S's is plane k_m0 itself."""
+        idx = order_stat_indices(samples.shape[1], level)
+        ks = [idx["k_lo"], idx["k_hi"], idx["k_m0"], idx["k_m1"]]
+        planes = ops.ensemble_order_stats(samples, ks)
+        B = samples.shape[0]
+        shape = (B,) + tuple(samples.shape[2:])
+        flat = planes.view(B, len(ks), 1, -1)
+
+        def pick(i):
+            if B == 1:
+                return planes[:, i]
+            return ops.gather_channel(flat, torch.tensor([i] * B, dtype=torch.int32).to(planes.device)).view(shape)
+
+        lo, hi, m0 = pick(0), pick(1), pick(2)
+        median = m0 if idx["k_m0"] == idx["k_m1"] else ops.axpby(m0, pick(3), 0.5, 0.5)
+        return dict(lo=lo, hi=hi, median=median, level=level, nominal=idx["nominal"], ks=ks)

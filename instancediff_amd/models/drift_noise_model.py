@@ -217,13 +217,18 @@ class CLIPDriftModel():
     @torch.no_grad()
     def test(self, **kw):  # :648-652
         """one restoration per input; with sde.num_samples > 1 (driftSDE) a posterior ensemble: output / get_visuals() are the per-pixel
-        mean of the members, output_std their spread, samples the members [B, S, ...] when called with return_samples=True"""
+        mean of the members, output_std their spread, samples the members [B, S, ...] when called with return_samples=True; with
+        sde.interval set as well, output_median / output_lo / output_hi are the per-pixel median and credible-interval maps (else None)"""
         self.output_std = self.samples = None
+        self.output_median = self.output_lo = self.output_hi = None
         if getattr(self.sde, "num_samples", 1) > 1:
             res = self.sde.reverse_ddpm_ensemble(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
                                                  optimize_type=self.optimize_type, image_context=self.A_emb, **kw)
             out, self.output_std = res[0], res[1]
             self.samples = res[2] if len(res) > 2 else None
+            stats = getattr(self.sde, "last_order_stats", None)
+            if stats is not None:
+                self.output_median, self.output_lo, self.output_hi = stats["median"], stats["lo"], stats["hi"]
         else:
             out = self.sde.reverse_ddpm(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
                                         optimize_type=self.optimize_type, image_context=self.A_emb, **kw)

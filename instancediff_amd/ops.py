@@ -23,6 +23,11 @@ ALGO_TRACE = None
 WGRAD_TRACE = None
 
 
+def launch_count():
+    """kernel launches this library has enqueued so far in the process (replays of a captured graph enqueue none)"""
+    return int(_lib.load().idiff_launch_count())
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -866,6 +871,57 @@ def ensemble_stats(x):
     std = torch.empty_like(mean)
     check(lib.idiff_ensemble_stats(_p(x), _p(mean), _p(std), B, S, x.numel() // (B * S), _stream()), "ensemble_stats")
     return mean, std
+
+
+ORDER_AUTO, ORDER_NETWORK, ORDER_RANK = 0, 1, 2
+
+
+def ensemble_order_stats(x, ks, algo=ORDER_AUTO, out=None):
+    """x [B, S, ...] -> [B, nk, ...]: plane i holds, per pixel, the ks[i]-th smallest (0-based) of the pixel's S values; 1 <= nk <= 8 host
+    ints in [0, S), any order, duplicates allowed.  algo: ORDER_AUTO | ORDER_NETWORK (S <= 16) | ORDER_RANK; the forms select the same
+    values.  A NaN among a pixel's S values makes every plane NaN there."""
+    lib = _lib.load()
+    _c(x, "x")
+    assert x.dim() >= 3, "ensemble_order_stats: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    ks = list(ks)
+    if any(not isinstance(k, int) or isinstance(k, bool) for k in ks):
+        raise _lib.IdiffError(f"ensemble_order_stats: ks must be ints, got {ks}")
+    if algo not in (ORDER_AUTO, ORDER_NETWORK, ORDER_RANK) or isinstance(algo, bool):
+        raise _lib.IdiffError(f"ensemble_order_stats: algo must be 0 (auto), 1 (network) or 2 (rank), got {algo!r}")
+    nk = len(ks)
+    shape = (B, nk) + tuple(x.shape[2:])
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    _c(out, "out")
+    assert tuple(out.shape) == shape, (tuple(out.shape), shape)
+    ks_host = (C.c_int32 * max(nk, 1))(*ks)
+    check(lib.idiff_ensemble_order_stats(_p(x), _p(out), B, S, x.numel() // (B * S), ks_host, nk, algo, _stream()), "ensemble_order_stats")
+    return out
+
+
+def interval_coverage(lo, hi, target):
+    """lo, hi, target [B, ...] -> int32 [B, 3] = per image the pixels of target (below lo, inside [lo, hi], above hi), exact counts; a
+    pixel where any of the three is NaN counts nowhere"""
+    lib = _lib.load()
+    _c(lo, "lo"), _c(hi, "hi"), _c(target, "target")
+    assert lo.dim() >= 2 and lo.shape == hi.shape == target.shape, "interval_coverage: lo, hi, target are [B, ...] of one shape"
+    B = lo.shape[0]
+    n_s = lo.numel() // B
+    counts = torch.empty((B, 3), device=lo.device, dtype=torch.int32)
+    ws = torch.empty((max(int(lib.idiff_interval_coverage_ws_ints(B, n_s)), 1),), device=lo.device, dtype=torch.int32)
+    check(lib.idiff_interval_coverage(_p(lo), _p(hi), _p(target), C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), B, n_s,
+                                      _stream()), "interval_coverage")
+    return counts
+
+
+def plane_sum(x):
+    """x [B, C, H, W] -> [B, C]: the sum over the pixels of every plane"""
+    lib = _lib.load()
+    B, Cc, H, W = x.shape
+    out = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
+    check(lib.idiff_plane_sum(_p(x), _bs(x, "x"), _p(out), B, Cc, H * W, _stream()), "plane_sum")
+    return out
 
 
 # ---- tiled sampling (include/idiff.h; the plan is models/SDEs/driftSDE.py's TilePlan, moved to the device by plan.to(device)) ----

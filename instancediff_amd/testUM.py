@@ -7,6 +7,8 @@ Reads `test: {iter, pth_dir, use_ema, which_model, which_sde, result_root}` (tes
 image of the test sets with `model.test()` (timed like :141-144), computes RMSE / PSNR / SSIM per image on the
 device (:151-164) and writes the LQ|pred|GT `.raw` triptychs (:170-173).  With `--num-samples S` (driftSDE) each image is restored as
 an S-member posterior ensemble: the metrics and the triptych are the mean's, `PSNR_member` / `STD` and a `<i>_std_WxHx1.raw` map are added.
+With `--interval L` on top of that the per-pixel median and the level-L credible interval of the members are written as `<i>_median_` / `<i>_lo_` /
+`<i>_hi_WxHx1.raw` maps, and `PSNR_median`, `COVER` (the share of ground-truth pixels inside the interval) and `WIDTH` (its mean width) are listed.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain.  With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
@@ -39,6 +41,9 @@ def main(argv=None):
                              "the per-pixel standard deviation is written next to it (overrides the YAML)")
     parser.add_argument("--max-batch", type=int, default=None, metavar="M",
                         help="driftSDE max_batch: rows per chain of an ensemble (overrides the YAML)")
+    parser.add_argument("--interval", type=float, default=None, metavar="L",
+                        help="driftSDE interval: credible level L in (0, 1) of the per-pixel interval and median maps of an ensemble, written "
+                             "next to the std map with PSNR_median / COVER / WIDTH (needs num_samples > 1; overrides the YAML)")
     parser.add_argument("--tile", type=int, nargs="+", default=None, metavar="P",
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
@@ -66,6 +71,8 @@ def main(argv=None):
         sde_opt['num_samples'] = args.num_samples
     if args.max_batch is not None:
         sde_opt['max_batch'] = args.max_batch
+    if args.interval is not None:
+        sde_opt['interval'] = args.interval
     if args.tile is not None:
         sde_opt['tile'] = args.tile[0] if len(args.tile) == 1 else list(args.tile)
     if args.tile_overlap is not None:
@@ -80,6 +87,10 @@ def main(argv=None):
     if S > 1:
         for r in results.values():
             r['PSNR_member'], r['STD'] = [], []
+    level = getattr(sde, 'interval', None) if S > 1 else None  # the interval maps are an ensemble's: the plain chain has none
+    if level is not None:
+        for r in results.values():
+            r['PSNR_median'], r['COVER'], r['WIDTH'] = [], [], []
     times = []
     n_done = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -116,17 +127,29 @@ def main(argv=None):
                     r['STD'].append(float(std_map.mean()))
                     std_map.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_std_{std_map.shape[-1]}x{std_map.shape[-2]}x1.raw"))
                     extra = f", PSNR_member={r['PSNR_member'][-1]}, STD={r['STD'][-1]}"
+                if level is not None:
+                    lo, hi, med = model.output_lo, model.output_hi, model.output_median
+                    npix = lo[0].numel()
+                    r['PSNR_median'].append(ops.image_metrics(med[:, 0], model.target[:, 0]).cpu().tolist()[0][1])
+                    r['COVER'].append(ops.interval_coverage(lo, hi, model.target).cpu().tolist()[0][1] / npix)
+                    r['WIDTH'].append(float(ops.plane_sum(ops.axpby(hi, lo, 1.0, -1.0)).cpu()[0, 0]) / npix)
+                    for tag, m in (("lo", lo), ("hi", hi), ("median", med)):
+                        m = m[0, 0].cpu()
+                        m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_{tag}_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
+                    extra += f", PSNR_median={r['PSNR_median'][-1]}, COVER={r['COVER'][-1]}, WIDTH={r['WIDTH'][-1]}"
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
                     break
     for k, v in results.items():
         if v['num']:
-            print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR') + (('PSNR_member', 'STD') if S > 1 else ())))
+            print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR') + (('PSNR_member', 'STD') if S > 1 else ())
+                                  + (('PSNR_median', 'COVER', 'WIDTH') if level is not None else ())))
     if times:
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
               + (f", {S} samples per image" if S > 1 else "")
+              + ("" if level is None else f", interval {level} (nominal {sde.last_order_stats['nominal']})")
               + ("" if getattr(sde, 'last_tiles', None) is None else ", {}x{} windows of {}x{}".format(*sde.last_tiles)))
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
