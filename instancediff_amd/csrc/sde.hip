@@ -103,6 +103,59 @@ __global__ __launch_bounds__(256) void irsde_step_kernel(const float* __restrict
     }
 }
 
+// ---- the driftSDE reverse update ----
+// Each piece of the update is defined once, here; the drift_step*_kernel forms below differ only in where their operands live.  Every
+// operation is rounded once, in the order written.
+struct StepCoef {
+    float a, b, c, rho_d, rho_s;
+    bool hist_d, hist_s;
+};
+
+// Row t = state[0] of coef [3][Tp1] = (a, b, c), or with HIST of coef [5][Tp1] = (a, b, c, rho_d, rho_s); without HIST rows 3-4 are never
+// read.  A rho != 0 turns that clock's history on -- true for NaN too: an off-schedule row poisons the result.
+template <bool HIST>
+__device__ __forceinline__ StepCoef load_step_coef(const float* __restrict__ coef, int Tp1, const int* __restrict__ state) {
+    const int t = state[0];
+    StepCoef k = {coef[t], coef[Tp1 + t], coef[2 * Tp1 + t], 0.f, 0.f, false, false};
+    if (HIST) {
+        k.rho_d = coef[3 * Tp1 + t];
+        k.rho_s = coef[4 * Tp1 + t];
+        k.hist_d = k.rho_d != 0.f;
+        k.hist_s = k.rho_s != 0.f;
+    }
+    return k;
+}
+
+// r + rho*(r - prev): one clock's prediction extrapolated linearly from the previous jump's
+__device__ __forceinline__ floatx4 extrapolate(floatx4 r, floatx4 prev, float rho) {
+    floatx4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = __fadd_rn(r[k], __fmul_rn(rho, __fsub_rn(r[k], prev[k])));
+    return o;
+}
+
+// z of one 4-element group: zero where c == 0 (nothing is read or drawn), injected() -- the form's load of its group of the injected
+// noise -- when there is a noise base, otherwise the Philox normals of (ctr, member)
+template <class Load>
+__device__ __forceinline__ floatx4 step_noise(float c, bool have_base, Load injected, uint64_t ctr, uint64_t seed, uint64_t member = 0) {
+    floatx4 zv = {0.f, 0.f, 0.f, 0.f};
+    if (c != 0.f) zv = have_base ? injected() : philox_normal4(ctr, seed, member);
+    return zv;
+}
+
+// o = ((x - a*R) - b*e) + c*z,  oa = o - cond
+__device__ __forceinline__ void step_update(floatx4 xv, floatx4 rt, floatx4 et, floatx4 zv, floatx4 cv, float a, float b, float c, floatx4& o,
+                                            floatx4& oa) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
+        r = __fsub_rn(r, __fmul_rn(b, et[k]));
+        r = __fadd_rn(r, __fmul_rn(c, zv[k]));
+        o[k] = r;
+        oa[k] = __fsub_rn(r, cv[k]);
+    }
+}
+
 __global__ __launch_bounds__(256) void drift_step_kernel(const float* __restrict__ x, const float* __restrict__ rh, const float* __restrict__ eh,
                                                          const float* __restrict__ z, const float* __restrict__ cond, float* __restrict__ xo,
                                                          float* __restrict__ xao, long long n, float a, float b, float c, uint64_t seed,
@@ -111,19 +164,11 @@ __global__ __launch_bounds__(256) void drift_step_kernel(const float* __restrict
     for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
         const long long i = v * 4;
         const floatx4 xv = ld4(x, i, n), rv = ld4(rh, i, n), ev = ld4(eh, i, n);
-        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
-        if (c != 0.f) zv = z ? ld4(z, i, n) : philox_normal4(offset + (uint64_t)v, seed);
+        const floatx4 zv = step_noise(c, z != nullptr, [&] { return ld4(z, i, n); }, offset + (uint64_t)v, seed);
         floatx4 o, oa;
         floatx4 cv = {0.f, 0.f, 0.f, 0.f};
         if (xao) cv = ld4(cond, i, n);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = __fsub_rn(xv[k], __fmul_rn(a, rv[k]));
-            r = __fsub_rn(r, __fmul_rn(b, ev[k]));
-            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
-            o[k] = r;
-            oa[k] = __fsub_rn(r, cv[k]);
-        }
+        step_update(xv, rv, ev, zv, cv, a, b, c, o, oa);
         st4(xo, i, n, o);
         if (xao) st4(xao, i, n, oa);
     }
@@ -132,51 +177,19 @@ __global__ __launch_bounds__(256) void drift_step_kernel(const float* __restrict
 // Graph-replayable form of the drift step: every per-step scalar comes from device memory, so ONE captured HIP graph of a
 // denoising step replays for every t.  state = {t, Philox call count, step index of this run}; coef = [3][Tp1] tables of
 // (a_t, b_t, c_t); injected noise (parity runs) is indexed by the step index.  In place: x <- update, xa <- x - cond
-// (element-wise, each thread reads before it writes its own element).  Same fp32 operation order as drift_step_kernel.
-__global__ __launch_bounds__(256) void drift_step_dev_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh,
-                                                             const float* __restrict__ zbase, const float* __restrict__ cond, float* xa, long long n,
-                                                             const float* __restrict__ coef, int Tp1, const int* __restrict__ state, uint64_t seed,
-                                                             uint64_t nper, uint64_t offset_base) {
-    const int t = state[0];
-    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
-    const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
-    const float* z = zbase ? zbase + (long long)state[2] * n : nullptr;
-    const long long nv = (n + 3) / 4;
-    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
-        const long long i = v * 4;
-        const floatx4 xv = ld4(x, i, n), rv = ld4(rh, i, n), ev = ld4(eh, i, n);
-        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
-        if (c != 0.f) zv = z ? ld4(z, i, n) : philox_normal4(offset + (uint64_t)v, seed);
-        const floatx4 cv = ld4(cond, i, n);
-        floatx4 o, oa;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = __fsub_rn(xv[k], __fmul_rn(a, rv[k]));
-            r = __fsub_rn(r, __fmul_rn(b, ev[k]));
-            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
-            o[k] = r;
-            oa[k] = __fsub_rn(r, cv[k]);
-        }
-        st4(x, i, n, o);
-        st4(xa, i, n, oa);
-    }
-}
-
-// Second-order multistep form of drift_step_dev_kernel (driftSDE solver_order = 2): coef = [5][Tp1] tables of (a, b, c, rho_d, rho_s);
-// each prediction is extrapolated linearly from the previous jump's, kept in rp / ep at fixed addresses for the next replay:
+// (element-wise, each thread reads before it writes its own element).
+// HIST is the second-order multistep form (driftSDE solver_order = 2): coef = [5][Tp1] tables of (a, b, c, rho_d, rho_s); each
+// prediction is extrapolated linearly from the previous jump's, kept in rp / ep at fixed addresses for the next replay:
 //   R~ = r + rho_d*(r - rp),  e~ = e + rho_s*(e - ep),  x <- ((x - a*R~) - b*e~) + c*z,  xa <- x - cond,  rp <- r,  ep <- e.
 // rho_d, rho_s are uniform over the grid.  A zero rho skips that clock's history read and its term (the first jump of a chain, a
-// flat level table), so with both zero the arithmetic is drift_step_dev_kernel's whatever rp / ep hold.  Element-wise and in place:
-// each thread reads its own elements before it writes them.
-__global__ __launch_bounds__(256) void drift_step2_dev_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh, float* rp,
-                                                              float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
-                                                              float* xa, long long n, const float* __restrict__ coef, int Tp1,
-                                                              const int* __restrict__ state, uint64_t seed, uint64_t nper,
-                                                              uint64_t offset_base) {
-    const int t = state[0];
-    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
-    const float rho_d = coef[3 * Tp1 + t], rho_s = coef[4 * Tp1 + t];
-    const bool hist_d = rho_d != 0.f, hist_s = rho_s != 0.f;  // true for NaN too: an off-schedule row poisons the result
+// flat level table), so with both zero the arithmetic is the 3-row form's whatever rp / ep hold.  Without HIST rp / ep are not touched.
+template <bool HIST>
+__global__ __launch_bounds__(256) void drift_step_dev_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh, float* rp,
+                                                             float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
+                                                             float* xa, long long n, const float* __restrict__ coef, int Tp1,
+                                                             const int* __restrict__ state, uint64_t seed, uint64_t nper,
+                                                             uint64_t offset_base) {
+    const StepCoef k = load_step_coef<HIST>(coef, Tp1, state);
     const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
     const float* z = zbase ? zbase + (long long)state[2] * n : nullptr;
     const long long nv = (n + 3) / 4;
@@ -184,32 +197,18 @@ __global__ __launch_bounds__(256) void drift_step2_dev_kernel(float* x, const fl
         const long long i = v * 4;
         const floatx4 xv = ld4(x, i, n), rv = ld4(rh, i, n), ev = ld4(eh, i, n);
         floatx4 rt = rv, et = ev;
-        if (hist_d) {
-            const floatx4 pv = ld4(rp, i, n);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
-        }
-        if (hist_s) {
-            const floatx4 pv = ld4(ep, i, n);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
-        }
-        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
-        if (c != 0.f) zv = z ? ld4(z, i, n) : philox_normal4(offset + (uint64_t)v, seed);
+        if (k.hist_d) rt = extrapolate(rv, ld4(rp, i, n), k.rho_d);
+        if (k.hist_s) et = extrapolate(ev, ld4(ep, i, n), k.rho_s);
+        const floatx4 zv = step_noise(k.c, z != nullptr, [&] { return ld4(z, i, n); }, offset + (uint64_t)v, seed);
         const floatx4 cv = ld4(cond, i, n);
         floatx4 o, oa;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
-            r = __fsub_rn(r, __fmul_rn(b, et[k]));
-            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
-            o[k] = r;
-            oa[k] = __fsub_rn(r, cv[k]);
-        }
+        step_update(xv, rt, et, zv, cv, k.a, k.b, k.c, o, oa);
         st4(x, i, n, o);
         st4(xa, i, n, oa);
-        st4(rp, i, n, rv);
-        st4(ep, i, n, ev);
+        if (HIST) {
+            st4(rp, i, n, rv);
+            st4(ep, i, n, ev);
+        }
     }
 }
 
@@ -426,18 +425,14 @@ __global__ __launch_bounds__(256) void ensemble_init_kernel(const float* __restr
     }
 }
 
-// drift_step_dev_kernel (HIST = false, coef [3][Tp1]) and drift_step2_dev_kernel (HIST = true, coef [5][Tp1]) with the z of row r
-// drawn from its member's stream at draw index j = 1 + state[1]; the arithmetic and its order are theirs.
+// drift_step_dev_kernel<HIST> on rows: the z of row r is drawn from its member's stream at draw index j = 1 + state[1].
 template <bool HIST>
 __global__ __launch_bounds__(256) void drift_step_members_kernel(float* x, const float* __restrict__ rh, const float* __restrict__ eh, float* rp,
                                                                  float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
                                                                  float* xa, long long Q, const float* __restrict__ coef, int Tp1,
                                                                  const int* __restrict__ state, const uint64_t* __restrict__ members,
                                                                  uint64_t seed) {
-    const int t = state[0];
-    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
-    const float rho_d = HIST ? coef[3 * Tp1 + t] : 0.f, rho_s = HIST ? coef[4 * Tp1 + t] : 0.f;
-    const bool hist_d = HIST && rho_d != 0.f, hist_s = HIST && rho_s != 0.f;  // true for NaN too, as in drift_step2_dev_kernel
+    const StepCoef k = load_step_coef<HIST>(coef, Tp1, state);
     const uint64_t m = members[blockIdx.y];
     const uint64_t q0 = (1ull + (uint64_t)(unsigned)state[1]) * (uint64_t)Q;
     const long long row0 = (long long)blockIdx.y * Q;  // in 4-element groups
@@ -452,28 +447,12 @@ __global__ __launch_bounds__(256) void drift_step_members_kernel(float* x, const
     for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
         const floatx4 xv = xv4[v], rv = r4[v], ev = e4[v];
         floatx4 rt = rv, et = ev;
-        if (hist_d) {
-            const floatx4 pv = rp4[v];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
-        }
-        if (hist_s) {
-            const floatx4 pv = ep4[v];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
-        }
-        floatx4 zv = {0.f, 0.f, 0.f, 0.f};
-        if (c != 0.f) zv = z ? z[v] : philox_normal4(q0 + (uint64_t)v, seed, m);
+        if (k.hist_d) rt = extrapolate(rv, rp4[v], k.rho_d);
+        if (k.hist_s) et = extrapolate(ev, ep4[v], k.rho_s);
+        const floatx4 zv = step_noise(k.c, z != nullptr, [&] { return z[v]; }, q0 + (uint64_t)v, seed, m);
         const floatx4 cv = c4[v];
         floatx4 o, oa;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
-            r = __fsub_rn(r, __fmul_rn(b, et[k]));
-            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
-            o[k] = r;
-            oa[k] = __fsub_rn(r, cv[k]);
-        }
+        step_update(xv, rt, et, zv, cv, k.a, k.b, k.c, o, oa);
         xv4[v] = o;
         xa4[v] = oa;
         if (HIST) {
@@ -606,8 +585,8 @@ __device__ __forceinline__ void blend_slot(const floatx4* __restrict__ src, long
 }
 
 // The tiled step.  Per float4 group v of the full image: blend the windows' predictions into R^ and e^ (slots (iy0,ix0), (iy0,ix1),
-// (iy1,ix0), (iy1,ix1) in that order, weight wy*wx), extrapolate them as drift_step2_dev_kernel does when HIST, draw z at the plain
-// chain's counter offset + v, update as drift_step_dev_kernel does, and scatter x and x - cond into every window whose extent holds
+// (iy1,ix0), (iy1,ix1) in that order, weight wy*wx), extrapolate them when HIST, draw z at the plain chain's counter offset + v,
+// update (the shared pieces above, as drift_step_dev_kernel<HIST>), and scatter x and x - cond into every window whose extent holds
 // the group.  Element-wise per pixel: a thread reads and writes only its own group of x / rp / ep and of each window's copy of it.
 template <bool HIST>
 __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const float* __restrict__ rt_, const float* __restrict__ et_, float* rp,
@@ -615,10 +594,7 @@ __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const f
                                                                float* __restrict__ xt_, float* __restrict__ xat_, long long nv, TileGeom g,
                                                                const float* __restrict__ coef, int Tp1, const int* __restrict__ state,
                                                                uint64_t seed, uint64_t nper, uint64_t offset_base) {
-    const int t = state[0];
-    const float a = coef[t], b = coef[Tp1 + t], c = coef[2 * Tp1 + t];
-    const float rho_d = HIST ? coef[3 * Tp1 + t] : 0.f, rho_s = HIST ? coef[4 * Tp1 + t] : 0.f;
-    const bool hist_d = HIST && rho_d != 0.f, hist_s = HIST && rho_s != 0.f;  // true for NaN too, as in drift_step2_dev_kernel
+    const StepCoef k = load_step_coef<HIST>(coef, Tp1, state);
     const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
     const floatx4* z4 = zbase ? reinterpret_cast<const floatx4*>(zbase) + (long long)state[2] * nv : nullptr;
     floatx4* x4p = reinterpret_cast<floatx4*>(x);
@@ -666,28 +642,12 @@ __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const f
         }
         const floatx4 xv = x4p[v];
         floatx4 rt = rv, et = ev;
-        if (hist_d) {
-            const floatx4 pv = rp4[v];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rt[k] = __fadd_rn(rv[k], __fmul_rn(rho_d, __fsub_rn(rv[k], pv[k])));
-        }
-        if (hist_s) {
-            const floatx4 pv = ep4[v];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) et[k] = __fadd_rn(ev[k], __fmul_rn(rho_s, __fsub_rn(ev[k], pv[k])));
-        }
-        floatx4 zv = zero4;
-        if (c != 0.f) zv = z4 ? z4[v] : philox_normal4(offset + (uint64_t)v, seed);
+        if (k.hist_d) rt = extrapolate(rv, rp4[v], k.rho_d);
+        if (k.hist_s) et = extrapolate(ev, ep4[v], k.rho_s);
+        const floatx4 zv = step_noise(k.c, z4 != nullptr, [&] { return z4[v]; }, offset + (uint64_t)v, seed);
         const floatx4 cv = c4[v];
         floatx4 o, oa;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float r = __fsub_rn(xv[k], __fmul_rn(a, rt[k]));
-            r = __fsub_rn(r, __fmul_rn(b, et[k]));
-            r = __fadd_rn(r, __fmul_rn(c, zv[k]));
-            o[k] = r;
-            oa[k] = __fsub_rn(r, cv[k]);
-        }
+        step_update(xv, rt, et, zv, cv, k.a, k.b, k.c, o, oa);
         x4p[v] = o;
         if (HIST) {
             rp4[v] = rv;
@@ -707,6 +667,22 @@ inline int stream_grid(long long nvec) {
     long long g = (nvec + 255) / 256;
     if (g < 1) g = 1;
     return (int)(g > 2048 ? 2048 : g);
+}
+
+// The history buffers of a 5-row step are read and rewritten element by element beside `others`, the operands the step reads or writes
+// at other addresses: they must be distinct from each other and from each of those.
+inline bool history_distinct(const float* r_prev, const float* e_prev, std::initializer_list<const void*> others) {
+    if (r_prev == e_prev) return false;
+    for (const void* p : others)
+        if (p == r_prev || p == e_prev) return false;
+    return true;
+}
+
+// coef_rows (3 or 5, checked by the caller) = 3 takes no history buffers, 5 needs both
+inline int check_coef_rows(const char* who, int coef_rows, const float* r_prev, const float* e_prev) {
+    IDIFF_CHECK_ARG(coef_rows == 5 || (!r_prev && !e_prev), "%s: coef_rows = 3 takes no history buffers", who);
+    IDIFF_CHECK_ARG(coef_rows == 3 || (r_prev && e_prev), "%s: coef_rows = 5 needs the history buffers", who);
+    return IDIFF_OK;
 }
 
 }  // namespace
@@ -787,8 +763,8 @@ extern "C" int idiff_drift_reverse_step_dev(float* x, const float* r_hat, const 
                                             int64_t n, const float* coef, int Tp1, const int32_t* state, uint64_t seed, uint64_t nper,
                                             uint64_t offset_base, idiff_stream_t stream) {
     IDIFF_CHECK_ARG(x && r_hat && e_hat && cond && xa && coef && state && n > 0 && Tp1 > 1, "drift_reverse_step_dev: bad args");
-    hipLaunchKernelGGL(drift_step_dev_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, z_base, cond, xa,
-                       (long long)n, coef, Tp1, state, seed, nper, offset_base);
+    hipLaunchKernelGGL(drift_step_dev_kernel<false>, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat,
+                       (float*)nullptr, (float*)nullptr, z_base, cond, xa, (long long)n, coef, Tp1, state, seed, nper, offset_base);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_dev");
     return IDIFF_OK;
 }
@@ -798,11 +774,10 @@ extern "C" int idiff_drift_reverse_step2_dev(float* x, const float* r_hat, const
                                              uint64_t seed, uint64_t nper, uint64_t offset_base, idiff_stream_t stream) {
     IDIFF_CHECK_ARG(x && r_hat && e_hat && r_prev && e_prev && cond && xa && coef5 && state && n > 0 && Tp1 > 1,
                     "drift_reverse_step2_dev: bad args");
-    IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_hat && r_prev != e_hat && e_prev != r_hat && e_prev != e_hat && r_prev != x && e_prev != x &&
-                        r_prev != xa && e_prev != xa,
+    IDIFF_CHECK_ARG(history_distinct(r_prev, e_prev, {r_hat, e_hat, x, xa}),
                     "drift_reverse_step2_dev: the history buffers must be distinct from each other and from every other operand");
-    hipLaunchKernelGGL(drift_step2_dev_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev,
-                       z_base, cond, xa, (long long)n, coef5, Tp1, state, seed, nper, offset_base);
+    hipLaunchKernelGGL(drift_step_dev_kernel<true>, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev,
+                       e_prev, z_base, cond, xa, (long long)n, coef5, Tp1, state, seed, nper, offset_base);
     IDIFF_CHECK_LAUNCH("drift_reverse_step2_dev");
     return IDIFF_OK;
 }
@@ -916,19 +891,13 @@ extern "C" int idiff_drift_reverse_step_tiled_dev(float* x, const float* r_tiles
     IDIFF_CHECK_ARG(x_tiles != xa_tiles && x_tiles != r_tiles && x_tiles != e_tiles && xa_tiles != r_tiles && xa_tiles != e_tiles &&
                         x != x_tiles && x != xa_tiles && x != r_tiles && x != e_tiles && x != cond,
                     "drift_reverse_step_tiled_dev: the image and the four window buffers must be distinct");
+    if (const int rc = check_coef_rows("drift_reverse_step_tiled_dev", coef_rows, r_prev, e_prev)) return rc;
+    IDIFF_CHECK_ARG(coef_rows == 3 || history_distinct(r_prev, e_prev, {r_tiles, e_tiles, x, x_tiles, xa_tiles}),
+                    "drift_reverse_step_tiled_dev: the history buffers must be distinct from each other and from every other operand");
     const long long nv = (long long)B * C * H * (W / 4);
-    if (coef_rows == 3) {
-        IDIFF_CHECK_ARG(!r_prev && !e_prev, "drift_reverse_step_tiled_dev: coef_rows = 3 takes no history buffers");
-        hipLaunchKernelGGL(drift_step_tiled_kernel<false>, dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev,
-                           e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed, nper, offset_base);
-    } else {
-        IDIFF_CHECK_ARG(r_prev && e_prev, "drift_reverse_step_tiled_dev: coef_rows = 5 needs the history buffers");
-        IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_tiles && r_prev != e_tiles && e_prev != r_tiles && e_prev != e_tiles && r_prev != x &&
-                            e_prev != x && r_prev != x_tiles && e_prev != x_tiles && r_prev != xa_tiles && e_prev != xa_tiles,
-                        "drift_reverse_step_tiled_dev: the history buffers must be distinct from each other and from every other operand");
-        hipLaunchKernelGGL(drift_step_tiled_kernel<true>, dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev,
-                           e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed, nper, offset_base);
-    }
+    hipLaunchKernelGGL(coef_rows == 3 ? drift_step_tiled_kernel<false> : drift_step_tiled_kernel<true>, dim3(stream_grid(nv)), dim3(256), 0,
+                       (hipStream_t)stream, x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed,
+                       nper, offset_base);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_tiled_dev");
     return IDIFF_OK;
 }
@@ -968,20 +937,12 @@ extern "C" int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat
     IDIFF_CHECK_ARG(n_s % 4 == 0, "drift_reverse_step_members_dev: n_s = %lld is not a multiple of 4", (long long)n_s);
     IDIFF_CHECK_ARG(aligned16({x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa}),
                     "drift_reverse_step_members_dev: operands must be 16-byte aligned");
-    const dim3 grid = rows_grid(n_s / 4, R);
+    if (const int rc = check_coef_rows("drift_reverse_step_members_dev", coef_rows, r_prev, e_prev)) return rc;
+    IDIFF_CHECK_ARG(coef_rows == 3 || history_distinct(r_prev, e_prev, {r_hat, e_hat, x, xa}),
+                    "drift_reverse_step_members_dev: the history buffers must be distinct from each other and from every other operand");
     const long long Q = n_s / 4;
-    if (coef_rows == 3) {
-        IDIFF_CHECK_ARG(!r_prev && !e_prev, "drift_reverse_step_members_dev: coef_rows = 3 takes no history buffers");
-        hipLaunchKernelGGL(drift_step_members_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond,
-                           xa, Q, coef, Tp1, state, members_dev, seed);
-    } else {
-        IDIFF_CHECK_ARG(r_prev && e_prev, "drift_reverse_step_members_dev: coef_rows = 5 needs the history buffers");
-        IDIFF_CHECK_ARG(r_prev != e_prev && r_prev != r_hat && r_prev != e_hat && e_prev != r_hat && e_prev != e_hat && r_prev != x &&
-                            e_prev != x && r_prev != xa && e_prev != xa,
-                        "drift_reverse_step_members_dev: the history buffers must be distinct from each other and from every other operand");
-        hipLaunchKernelGGL(drift_step_members_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond,
-                           xa, Q, coef, Tp1, state, members_dev, seed);
-    }
+    hipLaunchKernelGGL(coef_rows == 3 ? drift_step_members_kernel<false> : drift_step_members_kernel<true>, rows_grid(Q, R), dim3(256), 0,
+                       (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, Q, coef, Tp1, state, members_dev, seed);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_members_dev");
     return IDIFF_OK;
 }

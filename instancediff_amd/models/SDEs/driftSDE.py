@@ -78,24 +78,26 @@ def _step_coeffs(d, n, max_sigma, T, eta):
     return a.to(torch.float32), b.to(torch.float32), c.to(torch.float32)
 
 
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
 def _sample_schedule(T, sample_T=None, sample_timesteps=None):
     """-> [t_0, ..., t_K = 0] for the reverse chain, or None when neither option is set (the plain T-step chain).
     sample_T = K (1 <= K <= T): t_k = ((K - k) * T) // K, so t_0 = T, t_K = 0 and every gap is >= T // K.
     sample_timesteps: a strictly decreasing list of ints in [1, T]; 0 is appended."""
-    def is_int(v):
-        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
-    if sample_T is not None and is_int(sample_T) and sample_T == -1:
+    if sample_T is not None and _is_int(sample_T) and sample_T == -1:
         sample_T = None
     if sample_T is not None and sample_timesteps is not None:
         raise ValueError("driftSDE: set sample_T or sample_timesteps, not both")
     if sample_T is not None:
-        if not is_int(sample_T) or not 1 <= sample_T <= T:
+        if not _is_int(sample_T) or not 1 <= sample_T <= T:
             raise ValueError(f"driftSDE: sample_T must be an int in [1, T={T}] (or -1 / None: unset), got {sample_T!r}")
         K = int(sample_T)
         return [((K - k) * T) // K for k in range(K + 1)]
     if sample_timesteps is not None:
         ts = list(sample_timesteps)
-        if not ts or not all(is_int(t) and 1 <= t <= T for t in ts) or any(a <= b for a, b in zip(ts, ts[1:])):
+        if not ts or not all(_is_int(t) and 1 <= t <= T for t in ts) or any(a <= b for a, b in zip(ts, ts[1:])):
             raise ValueError(f"driftSDE: sample_timesteps must be a non-empty, strictly decreasing list of ints in [1, T={T}], got {sample_timesteps!r}")
         return [int(t) for t in ts] + [0]
     return None
@@ -105,7 +107,7 @@ def _solver_order(order):
     """1 (None: unset) or 2, as an int; anything else -- bools, floats and strings included -- is refused"""
     if order is None:
         return 1
-    if not isinstance(order, numbers.Integral) or isinstance(order, bool) or order not in (1, 2):
+    if not _is_int(order) or order not in (1, 2):
         raise ValueError(f"driftSDE: solver_order must be the int 1 or 2, got {order!r}")
     return int(order)
 
@@ -114,7 +116,7 @@ def _num_samples(num):
     """ensemble size as an int >= 1 (None: 1, off); bools, floats and strings are refused like solver_order's"""
     if num is None:
         return 1
-    if not isinstance(num, numbers.Integral) or isinstance(num, bool) or num < 1:
+    if not _is_int(num) or num < 1:
         raise ValueError(f"driftSDE: num_samples must be an int >= 1 (or None: off), got {num!r}")
     return int(num)
 
@@ -144,13 +146,9 @@ def order_stat_indices(S, level):
 
 
 def _max_batch(rows):
-    if not isinstance(rows, numbers.Integral) or isinstance(rows, bool) or rows < 1:
+    if not _is_int(rows) or rows < 1:
         raise ValueError(f"driftSDE: max_batch must be an int >= 1, got {rows!r}")
     return int(rows)
-
-
-def _is_int(v):
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
 
 def _tile_size(tile):
@@ -498,38 +496,45 @@ class driftSDE:
             if timesteps is None:
                 self.next_t = None
                 t0 = sde.T if t_start is None else int(t_start)
-                self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
                 self.coef = torch.stack([sde._a, sde._b, sde._c]).to(device=dev, dtype=torch.float32).contiguous()
             else:
                 ts = list(timesteps)
                 if t_start is not None or len(ts) < 2 or ts[-1] != 0 or ts[0] > sde.T or any(a <= b for a, b in zip(ts, ts[1:])):
                     raise ValueError(f"Stepper: timesteps must decrease strictly from at most T={sde.T} to 0 (no t_start), got {ts}")
                 t0 = self.t_first = ts[0]
-                self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
                 coef, next_t = sde._schedule_tables(ts, self.order)
                 self.coef = coef.to(dev).contiguous()
                 self.next_t = next_t.to(dev).contiguous()
+            self.tdev = torch.full((x.shape[0],), float(t0), dtype=torch.float32, device=dev)
             self.state = torch.tensor([t0, 0, 0], dtype=torch.int32, device=dev)  # {t, draws of this run, step index}
             self.noises = None if noises is None else noises.contiguous()
             self.nper = (x.numel() + 3) // 4
             self.off_base = sde._off  # this run's draws start where the stream's earlier ones ended
             self.graph = None
             self.steps_done = 0
-            if self.order == 2:  # the previous jump's predictions; not read at t_0, whose rho rows are 0
-                self.r_prev, self.e_prev = torch.empty_like(x), torch.empty_like(x)
+            # order 2: the previous jump's predictions; not read at t_0, whose rho rows are 0
+            self.r_prev, self.e_prev = (torch.empty_like(x), torch.empty_like(x)) if self.order == 2 else (None, None)
 
         def _body(self):
-            sde = self.sde
-            r_hat, e_hat = sde.predict(self.xa, self.x, self.cond, self.tdev, self.names, self.text_encoder, self.ctx)
+            self._update(*self._predict())
+            self._advance()
+
+        def _predict(self):
+            return self.sde.predict(self.xa, self.x, self.cond, self.tdev, self.names, self.text_encoder, self.ctx)
+
+        def _update(self, r_hat, e_hat):
+            """the fused update of x / xa from this step's predictions: the member, second-order or plain step"""
+            seed = self.sde.seed
             if self.members is not None:
-                hist = (self.r_prev, self.e_prev) if self.order == 2 else (None, None)
-                ops.drift_reverse_step_members_dev(self.x, r_hat, e_hat, hist[0], hist[1], self.noises, self.cond, self.xa, self.coef, self.state,
-                                                   self.members, sde.seed)
+                ops.drift_reverse_step_members_dev(self.x, r_hat, e_hat, self.r_prev, self.e_prev, self.noises, self.cond, self.xa, self.coef,
+                                                   self.state, self.members, seed)
             elif self.order == 2:
                 ops.drift_reverse_step2_dev(self.x, r_hat, e_hat, self.r_prev, self.e_prev, self.noises, self.cond, self.xa, self.coef, self.state,
-                                            sde.seed, self.nper, self.off_base)
+                                            seed, self.nper, self.off_base)
             else:
-                ops.drift_reverse_step_dev(self.x, r_hat, e_hat, self.noises, self.cond, self.xa, self.coef, self.state, sde.seed, self.nper, self.off_base)
+                ops.drift_reverse_step_dev(self.x, r_hat, e_hat, self.noises, self.cond, self.xa, self.coef, self.state, seed, self.nper, self.off_base)
+
+        def _advance(self):
             if self.next_t is None:
                 ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
             else:
@@ -631,24 +636,20 @@ class driftSDE:
             if len(self.chunks) > 1:
                 self.r_tiles, self.e_tiles = torch.empty_like(self.x_tiles), torch.empty_like(self.x_tiles)
 
-        def _body(self):
-            sde = self.sde
+        def _predict(self):
             for r0, r1, names, ctx in self.chunks:
-                r_hat, e_hat = sde.predict(self.xa_tiles[r0:r1], self.x_tiles[r0:r1], self.cond_tiles[r0:r1], self.tdev[r0:r1], names,
-                                           self.text_encoder, ctx)
+                r_hat, e_hat = self.sde.predict(self.xa_tiles[r0:r1], self.x_tiles[r0:r1], self.cond_tiles[r0:r1], self.tdev[r0:r1], names,
+                                                self.text_encoder, ctx)
                 if len(self.chunks) == 1:
-                    r_tiles, e_tiles = r_hat, e_hat
-                else:  # 1*r + 0*r: a copy by a library launch, into the rows the step reads
-                    r_tiles, e_tiles = self.r_tiles, self.e_tiles
-                    ops.axpby(r_hat, r_hat, 1.0, 0.0, out=r_tiles[r0:r1])
-                    ops.axpby(e_hat, e_hat, 1.0, 0.0, out=e_tiles[r0:r1])
-            hist = (self.r_prev, self.e_prev) if self.order == 2 else (None, None)
-            ops.drift_reverse_step_tiled_dev(self.x, r_tiles, e_tiles, hist[0], hist[1], self.noises, self.cond, self.x_tiles, self.xa_tiles,
-                                             self.plan, self.coef, self.state, sde.seed, self.nper, self.off_base)
-            if self.next_t is None:
-                ops.step_state_advance(self.state, self.tdev, self.T, self.t_stop)
-            else:
-                ops.step_state_advance_table(self.state, self.tdev, self.next_t, self.t_first, self.t_stop)
+                    return r_hat, e_hat
+                # 1*r + 0*r: a copy by a library launch, into the rows the step reads
+                ops.axpby(r_hat, r_hat, 1.0, 0.0, out=self.r_tiles[r0:r1])
+                ops.axpby(e_hat, e_hat, 1.0, 0.0, out=self.e_tiles[r0:r1])
+            return self.r_tiles, self.e_tiles
+
+        def _update(self, r_tiles, e_tiles):
+            ops.drift_reverse_step_tiled_dev(self.x, r_tiles, e_tiles, self.r_prev, self.e_prev, self.noises, self.cond, self.x_tiles,
+                                             self.xa_tiles, self.plan, self.coef, self.state, self.sde.seed, self.nper, self.off_base)
 
     def _chain_plan(self, reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm"):
         """-> (schedule or None, steps, solver order) of a reverse chain down to T_stop, after the option checks"""
@@ -671,6 +672,17 @@ class driftSDE:
             nsteps = self.T - T_stop
         return sched, nsteps, order
 
+    def _start_state(self, cond, x_T):
+        """a private copy of x_T, drawn as cond + max_sigma*z from the sde's stream when none is given"""
+        if x_T is None:
+            x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
+        return x_T.contiguous().clone()
+
+    def _record_run(self, stepper, nsteps, order):
+        self.last_mode = stepper.mode  # 'graph' | 'eager': how the loop of this call ran
+        self.last_steps = nsteps
+        self.last_solver_order = order
+
     @torch.no_grad()
     def reverse_ddpm(self, cond, names, text_encoder, reverse_type="std", optimize_type="inputRes", image_context=None, x_T=None,
                      noises=None, T_stop=0):
@@ -684,20 +696,12 @@ class driftSDE:
                                            image_context=image_context, x_T=x_T, noises=noises, T_stop=T_stop)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop)
         cond = cond.contiguous()
-        B = cond.shape[0]
-        if x_T is None:
-            x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
-        x = x_T.contiguous().clone()
+        x = self._start_state(cond, x_T)
         self.last_tiles = None
-        if sched is None:
-            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop)
-        else:
-            stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched,
-                                       solver_order=order)
+        stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched,
+                                   solver_order=order)
         out = stepper.run(nsteps)
-        self.last_mode = stepper.mode  # 'graph' | 'eager': how the loop of this call ran
-        self.last_steps = nsteps
-        self.last_solver_order = order
+        self._record_run(stepper, nsteps, order)
         return out
 
     @torch.no_grad()
@@ -719,18 +723,14 @@ class driftSDE:
         if W % 4:
             raise ValueError(f"reverse_ddpm_tiled: the image width {W} is not a multiple of 4")
         plan = self._tile_plan(H, W, cond.device)
-        if x_T is None:
-            x_T = ops.axpby(cond, self._randn_like(cond), 1.0, self.max_sigma)
-        x = x_T.contiguous().clone()
+        x = self._start_state(cond, x_T)
         nwin = plan.ny * plan.nx
         names_rep = [n for n in names for _ in range(nwin)]
         ctx_rep = None if image_context is None else image_context.repeat_interleave(nwin, dim=0)
         stepper = driftSDE.TiledStepper(self, x, cond, plan, names_rep, text_encoder, ctx_rep, noises=noises, t_stop=T_stop, timesteps=sched,
                                         solver_order=order)
         out = stepper.run(nsteps)
-        self.last_mode = stepper.mode
-        self.last_steps = nsteps
-        self.last_solver_order = order
+        self._record_run(stepper, nsteps, order)
         self.last_tiles = plan.grid
         return out
 
@@ -779,9 +779,7 @@ class driftSDE:
                                        noises=None if noises is None else noises[:, r0:r1].contiguous(), t_stop=T_stop, timesteps=sched,
                                        solver_order=order, members=mdev[r0:r1], xa=xa[r0:r1])
             stepper.run(nsteps)
-        self.last_mode = stepper.mode
-        self.last_steps = nsteps
-        self.last_solver_order = order
+        self._record_run(stepper, nsteps, order)
         self.last_members = torch.tensor(ids, dtype=torch.int64).view(B, S)
         samples = x.view((B, S) + tuple(cond.shape[1:]))
         mean, std = ops.ensemble_stats(samples)

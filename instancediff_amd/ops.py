@@ -785,11 +785,16 @@ def drift_reverse_step(x, r_hat, e_hat, z, a, b, c, cond=None, seed=0, offset=0,
     return (out, xa_out) if cond is not None else out
 
 
+def _step_tables(coef, rows, state):
+    """the device-state drift steps' shared assertion: `coef` [one of `rows`, T+1] and `state` int32 [3] on the GPU"""
+    assert state.dtype == torch.int32 and state.is_cuda and state.numel() == 3 and coef.dim() == 2 and coef.shape[0] in rows
+
+
 def drift_reverse_step_dev(x, r_hat, e_hat, z_base, cond, xa, coef, state, seed, nper, offset_base=0):
     """in-place, graph-replayable drift step: per-step scalars from `coef` [3, T+1] and `state` int32 [3] on the device"""
     lib = _lib.load()
     _c(x, "x"), _c(r_hat, "r_hat"), _c(e_hat, "e_hat"), _c(z_base, "z"), _c(cond, "cond"), _c(xa, "xa"), _c(coef, "coef")
-    assert state.dtype == torch.int32 and state.is_cuda and state.numel() == 3 and coef.dim() == 2 and coef.shape[0] == 3
+    _step_tables(coef, (3,), state)
     check(lib.idiff_drift_reverse_step_dev(_p(x), _p(r_hat), _p(e_hat), _p(z_base), _p(cond), _p(xa), x.numel(), _p(coef), coef.shape[1],
                                            C.c_void_p(state.data_ptr()), seed, nper, offset_base, _stream()), "drift_reverse_step_dev")
 
@@ -800,7 +805,7 @@ def drift_reverse_step2_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, c
     lib = _lib.load()
     _c(x, "x"), _c(r_hat, "r_hat"), _c(e_hat, "e_hat"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
     _c(xa, "xa"), _c(coef5, "coef5")
-    assert state.dtype == torch.int32 and state.is_cuda and state.numel() == 3 and coef5.dim() == 2 and coef5.shape[0] == 5
+    _step_tables(coef5, (5,), state)
     assert r_prev.numel() == x.numel() and e_prev.numel() == x.numel()
     check(lib.idiff_drift_reverse_step2_dev(_p(x), _p(r_hat), _p(e_hat), _p(r_prev), _p(e_prev), _p(z_base), _p(cond), _p(xa), x.numel(),
                                             _p(coef5), coef5.shape[1], C.c_void_p(state.data_ptr()), seed, nper, offset_base, _stream()),
@@ -852,7 +857,7 @@ def drift_reverse_step_members_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond
     _c(x, "x"), _c(r_hat, "r_hat"), _c(e_hat, "e_hat"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
     _c(xa, "xa"), _c(coef, "coef"), _c(state, "state", torch.int32)
     R = x.shape[0]
-    assert state.numel() == 3 and coef.dim() == 2 and coef.shape[0] in (3, 5)
+    _step_tables(coef, (3, 5), state)
     for t in (r_hat, e_hat, r_prev, e_prev, cond, xa):
         assert t is None or t.numel() == x.numel()
     assert z_base is None or z_base.numel() % x.numel() == 0
@@ -960,7 +965,7 @@ def drift_reverse_step_tiled_dev(x, r_tiles, e_tiles, r_prev, e_prev, z_base, co
     _c(x_tiles, "x_tiles"), _c(xa_tiles, "xa_tiles"), _c(coef, "coef"), _c(state, "state", torch.int32)
     dims = _tile_args(plan, x, "drift_reverse_step_tiled_dev")
     nt = dims[0] * plan.ny * plan.nx * dims[1] * plan.Ph * plan.Pw
-    assert state.numel() == 3 and coef.dim() == 2 and coef.shape[0] in (3, 5)
+    _step_tables(coef, (3, 5), state)
     for t in (r_tiles, e_tiles, x_tiles, xa_tiles):
         assert t.numel() == nt, (t.numel(), nt)
     for t in (r_prev, e_prev, cond):
