@@ -492,6 +492,24 @@ int idiff_randn_members(float* out, int R, int64_t n_s, const uint64_t* members_
  * by idiff_axpby(cond_rep, z, 1, sigma) and idiff_axpby(x, cond_rep, 1, -1). */
 int idiff_ensemble_init(const float* cond, float* cond_rep, float* x, float* xa, int B, int S, int64_t n_s, const uint64_t* members_dev,
                         float sigma, uint64_t seed, idiff_stream_t stream);
+/* The start of an image in a chain whose buffers and captured step graph outlive the call (driftSDE reuse_graph): the
+ * x_T construction into the chain's own cond / x / xa and the device state of its first step, in ONE launch.
+ * Plain chain (members_dev == NULL): S == 1, row0 == 0, R == B are required; n = B*n_s >= 1 is any size (a tail of n % 4 elements is
+ *   handled element-wise, as in idiff_randn).  z is the library's one stream at counters offset + v over the flattened batch:
+ *   cond = cond_in ;  x = 1*cond_in + sigma*z ;  xa = x - cond_in, bit-identical to idiff_randn(z, n, seed, offset) followed by
+ *   idiff_axpby(cond_in, z, 1, sigma) and idiff_axpby(x, cond_in, 1, -1).
+ * Member chain: output row r (0 <= r < R) is row row0 + r of the B*S ensemble rows: it reads cond_in[(row0 + r) / S] and draws from
+ *   member members_dev[r] at j = 0; 0 <= row0, row0 + R <= B*S and n_s % 4 == 0 are required; `offset` is not read.  Bit-identical to
+ *   rows [row0, row0 + R) of idiff_ensemble_init given those rows' member ids (the two kernels share their body).
+ * Both: state = {t0, calls0, 0} and tdev[0..R) = (float)t0 are written by one block of the same launch (no block of it reads them):
+ *   the first step of the chain then runs at t0 and, in the plain chain, draws the counters offset_base + calls0*nper + v of
+ *   idiff_drift_reverse_step_dev; a member chain passes calls0 = 0 (its steps draw at j = 1 + state[1]).
+ *   0 < R <= 65535, t0 >= 0, calls0 >= 0; cond_in, cond, x, xa 16-byte aligned and pairwise distinct (cond_in is only read).
+ *   256 threads, one float4 per lane, grid-stride; no LDS, no atomics.  A refused call (IDIFF_E_BADARG) launches nothing and leaves
+ *   every buffer as it was. */
+int idiff_chain_begin(const float* cond_in, float* cond, float* x, float* xa, int B, int S, int64_t n_s, int64_t row0, int R,
+                      const uint64_t* members_dev, float sigma, uint64_t seed, uint64_t offset, int32_t* state, float* tdev, int t0,
+                      int calls0, idiff_stream_t stream);
 /* idiff_drift_reverse_step_dev (coef_rows = 3, r_prev = e_prev = NULL) or idiff_drift_reverse_step2_dev (coef_rows = 5) on R rows with
  * the z of row r drawn from member members_dev[r]'s stream at j = 1 + state[1].  Same arithmetic, order and history handling; with z_base
  * ([steps][R*n_s], indexed by state[2]) the result is bit-identical to that entry point on the same operands. */

@@ -128,6 +128,7 @@ SIGNATURES = {
     "idiff_drift_reverse_step2_dev": (I, [P, P, P, P, P, P, P, P, I64, P, I, P, U64, U64, U64, c_stream]),
     "idiff_randn_members": (I, [P, I, I64, P, U64, U64, c_stream]),
     "idiff_ensemble_init": (I, [P, P, P, P, I, I, I64, P, F, U64, c_stream]),
+    "idiff_chain_begin": (I, [P, P, P, P, I, I, I64, I64, I, P, F, U64, U64, P, P, I, I, c_stream]),
     "idiff_drift_reverse_step_members_dev": (I, [P, P, P, P, P, P, P, P, I, I64, P, I, I, P, P, U64, c_stream]),
     "idiff_ensemble_stats": (I, [P, P, P, I, I, I64, c_stream]),
     "idiff_ensemble_order_stats": (I, [P, P, I, I, I64, C.POINTER(C.c_int32), I, I, c_stream]),

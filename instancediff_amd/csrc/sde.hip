@@ -401,27 +401,68 @@ __global__ __launch_bounds__(256) void randn_members_kernel(float* __restrict__ 
         o[v] = philox_normal4(j * (uint64_t)Q + (uint64_t)v, seed, m);
 }
 
-// row b*S + s:  cond_rep = cond[b],  x = 1*cond + sigma*z(member, j = 0),  xa = x - cond  (axpby's products by 1 and -1 are exact)
-__global__ __launch_bounds__(256) void ensemble_init_kernel(const float* __restrict__ cond, float* __restrict__ cond_rep, float* __restrict__ x,
-                                                            float* __restrict__ xa, int S, long long Q, const uint64_t* __restrict__ members,
-                                                            float sigma, uint64_t seed) {
-    const long long row = blockIdx.y;
-    const uint64_t m = members[row];
-    const floatx4* c = reinterpret_cast<const floatx4*>(cond) + (row / S) * Q;
+// the start of a chain from a cond group and its x_T draw:  x = 1*cond + sigma*z,  xa = x - cond  (axpby's products by 1 and -1 are exact)
+__device__ __forceinline__ void chain_start4(floatx4 cv, floatx4 zv, float sigma, floatx4& o, floatx4& oa) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        o[k] = __fadd_rn(cv[k], __fmul_rn(sigma, zv[k]));
+        oa[k] = __fsub_rn(o[k], cv[k]);
+    }
+}
+
+// output row `row` of a member chain's start from cond row `src`: cond_rep = cond, x and xa from member m's draw j = 0 (chain_start4)
+__device__ __forceinline__ void member_row_start(const float* __restrict__ cond, float* __restrict__ cond_rep, float* __restrict__ x,
+                                                 float* __restrict__ xa, long long src, long long row, long long Q, uint64_t m, float sigma,
+                                                 uint64_t seed) {
+    const floatx4* c = reinterpret_cast<const floatx4*>(cond) + src * Q;
     floatx4* cr = reinterpret_cast<floatx4*>(cond_rep) + row * Q;
     floatx4* xo = reinterpret_cast<floatx4*>(x) + row * Q;
     floatx4* xao = reinterpret_cast<floatx4*>(xa) + row * Q;
     for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
         const floatx4 cv = c[v], zv = philox_normal4((uint64_t)v, seed, m);
         floatx4 o, oa;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o[k] = __fadd_rn(cv[k], __fmul_rn(sigma, zv[k]));
-            oa[k] = __fsub_rn(o[k], cv[k]);
-        }
+        chain_start4(cv, zv, sigma, o, oa);
         cr[v] = cv;
         xo[v] = o;
         xao[v] = oa;
+    }
+}
+
+// row b*S + s:  cond_rep = cond[b],  x = 1*cond + sigma*z(member, j = 0),  xa = x - cond
+__global__ __launch_bounds__(256) void ensemble_init_kernel(const float* __restrict__ cond, float* __restrict__ cond_rep, float* __restrict__ x,
+                                                            float* __restrict__ xa, int S, long long Q, const uint64_t* __restrict__ members,
+                                                            float sigma, uint64_t seed) {
+    const long long row = blockIdx.y;
+    member_row_start(cond, cond_rep, x, xa, row / S, row, Q, members[row], sigma, seed);
+}
+
+// The start of an image in a held chain (idiff_chain_begin): the x_T construction into the chain's own buffers plus the device state
+// of its first step, in one launch.  MEMBERS: grid (chunks, R), output row r is ensemble row row0 + r (member_row_start); otherwise a
+// flat grid over the n elements of the batch with the plain stream's counters offset + v, tail by ld4 / st4 as in randn_kernel.
+// Block (0, 0) also writes state = {t0, calls0, 0} and tdev[0..R) = t0; no block of this launch reads either.
+template <bool MEMBERS>
+__global__ __launch_bounds__(256) void chain_begin_kernel(const float* __restrict__ cond_in, float* __restrict__ cond, float* __restrict__ x,
+                                                          float* __restrict__ xa, long long n, int S, long long Q, long long row0, int R,
+                                                          const uint64_t* __restrict__ members, float sigma, uint64_t seed, uint64_t offset,
+                                                          int* __restrict__ state, float* __restrict__ tdev, int t0, int calls0) {
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        for (int i = threadIdx.x; i < R; i += blockDim.x) tdev[i] = (float)t0;
+        if (threadIdx.x < 3) state[threadIdx.x] = threadIdx.x == 0 ? t0 : (threadIdx.x == 1 ? calls0 : 0);
+    }
+    if (MEMBERS) {
+        const long long row = blockIdx.y;
+        member_row_start(cond_in, cond, x, xa, (row0 + row) / S, row, Q, members[row], sigma, seed);
+    } else {
+        const long long nv = (n + 3) / 4;
+        for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
+            const long long i = v * 4;
+            const floatx4 cv = ld4(cond_in, i, n), zv = philox_normal4(offset + (uint64_t)v, seed);
+            floatx4 o, oa;
+            chain_start4(cv, zv, sigma, o, oa);
+            st4(cond, i, n, cv);
+            st4(x, i, n, o);
+            st4(xa, i, n, oa);
+        }
     }
 }
 
@@ -924,6 +965,31 @@ extern "C" int idiff_ensemble_init(const float* cond, float* cond_rep, float* x,
     hipLaunchKernelGGL(ensemble_init_kernel, rows_grid(n_s / 4, (long long)B * S), dim3(256), 0, (hipStream_t)stream, cond, cond_rep, x, xa, S,
                        (long long)(n_s / 4), members_dev, sigma, seed);
     IDIFF_CHECK_LAUNCH("ensemble_init");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_chain_begin(const float* cond_in, float* cond, float* x, float* xa, int B, int S, int64_t n_s, int64_t row0, int R,
+                                 const uint64_t* members_dev, float sigma, uint64_t seed, uint64_t offset, int32_t* state, float* tdev, int t0,
+                                 int calls0, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(cond_in && cond && x && xa && state && tdev && B > 0 && S > 0 && n_s > 0 && R > 0 && R <= 65535 && t0 >= 0 && calls0 >= 0,
+                    "chain_begin: bad args");
+    IDIFF_CHECK_ARG(aligned16({cond_in, cond, x, xa}), "chain_begin: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(cond != x && cond != xa && x != xa && cond_in != cond && cond_in != x && cond_in != xa,
+                    "chain_begin: cond_in and the three outputs must be distinct");
+    if (!members_dev) {
+        IDIFF_CHECK_ARG(S == 1 && row0 == 0 && R == B, "chain_begin: the plain chain takes S = 1, row0 = 0, R = B (got S = %d, row0 = %lld, R = %d, B = %d)",
+                        S, (long long)row0, R, B);
+        const long long n = (long long)B * n_s;
+        hipLaunchKernelGGL(chain_begin_kernel<false>, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, cond_in, cond, x, xa, n, 1,
+                           0ll, 0ll, R, members_dev, sigma, seed, offset, state, tdev, t0, calls0);
+    } else {
+        IDIFF_CHECK_ARG(n_s % 4 == 0, "chain_begin: n_s = %lld is not a multiple of 4", (long long)n_s);
+        IDIFF_CHECK_ARG(row0 >= 0 && row0 + R <= (long long)B * S, "chain_begin: rows [%lld, %lld) are not rows of the %d x %d ensemble",
+                        (long long)row0, (long long)row0 + R, B, S);
+        hipLaunchKernelGGL(chain_begin_kernel<true>, rows_grid(n_s / 4, R), dim3(256), 0, (hipStream_t)stream, cond_in, cond, x, xa, 0ll, S,
+                           (long long)(n_s / 4), (long long)row0, R, members_dev, sigma, seed, offset, state, tdev, t0, calls0);
+    }
+    IDIFF_CHECK_LAUNCH("chain_begin");
     return IDIFF_OK;
 }
 

@@ -33,11 +33,19 @@ next step's window inputs out again -- one fused kernel per step beside the nets
 Credible intervals (`interval: L`): with it reverse_ddpm_ensemble also selects, per pixel, the order statistics of the S
 members that bracket the central level-L interval and the median (one launch, values selected and never rounded) into
 self.last_order_stats.  order_stat_indices states which order statistics those are and the coverage they nominally give.
+
+Graph reuse (`reuse_graph: true`): with it the sde keeps the captured step graph, the buffers it is baked on and the cache
+values it reads in a Session per configuration, and a later image of the same shape only refills the buffers (one ops.chain_begin
+launch) and replays.  The bits are those of the per-call path; what changes is who owns the graph's memory: the sde, until
+close_sessions().
 """
+import collections
 import fractions
+import itertools
 import math
 import numbers
 import os
+import weakref
 
 import torch
 
@@ -284,16 +292,70 @@ def _jump_tables(d, n, max_sigma, T, eta, timesteps, order=1):
     return coef.to(torch.float32), next_t
 
 
+def _reuse_graph(flag):
+    """the reuse_graph option as a bool (None: False); anything but a bool is refused"""
+    if flag is None:
+        return False
+    if not isinstance(flag, bool):
+        raise ValueError(f"driftSDE: reuse_graph must be true or false (or None: false), got {flag!r}")
+    return flag
+
+
+MAX_SESSIONS = 4  # held step graphs per sde; the least recently used is closed first
+
+
+def session_calls0(off, off0, nper, nsteps=0):
+    """state[1] at the start of an image in a held plain chain.  Its step kernel has offset_base = off0 and nper baked in and draws the
+    counters off0 + state[1]*nper + v; a fresh Stepper would draw off + step*nper + v.  The two agree for state[1] = (off - off0) / nper,
+    which is returned when it is exact, not negative and, with the chain's nsteps advances on top, still fits the 31 bits of the device
+    word; otherwise None: the session cannot serve this stream position and a new one is captured (a draw of another size went through
+    the stream in between, or the stream was rewound)."""
+    diff = off - off0
+    if nper < 1 or diff < 0 or diff % nper:
+        return None
+    q = diff // nper
+    return q if q + nsteps < 1 << 31 else None
+
+
+def _core(net):
+    """the UNet behind a net of the sde (an EMA wrapper forwards to its ema_model)"""
+    return getattr(net, "ema_model", net)
+
+
+def weights_signature(modules):
+    """what a held graph's packed weights and cached vectors were built from: train_ops.WEIGHT_EPOCH plus (data_ptr, _version) of every
+    parameter and buffer of `modules` (objects without parameters contribute nothing).  model.load(), an optimizer step or an in-place
+    edit changes it."""
+    from ... import train_ops
+    sig = [train_ops.WEIGHT_EPOCH[0]]
+    for m in modules:
+        if hasattr(m, "parameters") and hasattr(m, "buffers"):
+            sig.extend((t.data_ptr(), t._version) for t in itertools.chain(m.parameters(), m.buffers()))
+    return tuple(sig)
+
+
+def session_key(sde, kind, rows, chw, ctx_shape, sched, order, T_stop, text_encoder, device):
+    """The configuration a held step graph serves; a call reuses a session only under an equal key.  The weights signature comes last."""
+    nets = (sde.drift_net, sde.noise_net)
+    cores = [_core(n) for n in nets]
+    smms = [m for c in cores if hasattr(c, "score_map_modules") for m in c.score_map_modules()]
+    return (kind, int(rows), tuple(chw), None if ctx_shape is None else tuple(ctx_shape), None if sched is None else tuple(sched), int(order),
+            int(T_stop), int(sde.seed), (sde.T, sde.max_sigma, sde.eta) + tuple(sde.schedule_names), bool(sde.two_streams), str(device),
+            tuple(id(n) for n in nets) + (id(text_encoder),), tuple(getattr(c, "conv_dtype", None) for c in cores),
+            weights_signature(cores + smms + [text_encoder]))
+
+
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
                  sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, tile=None, tile_overlap=None,
-                 interval=None, **_ignored):
+                 interval=None, reuse_graph=None, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
         nets = nets or {}
         self.drift_net = nets.get("drift_net")
         self.noise_net = nets.get("noise_net")
+        self.schedule_names = (str(drift_schedule), str(noise_schedule))
         self._h_drift = _level_table(self.T, drift_schedule)
         self._h_noise = _level_table(self.T, noise_schedule)
         self._a, self._b, self._c = _step_coeffs(self._h_drift, self._h_noise, self.max_sigma, self.T, self.eta)
@@ -319,6 +381,29 @@ class driftSDE:
         self.set_tiling(tile, tile_overlap)
         self.last_order_stats = None
         self.set_interval(interval)
+        self._sessions = collections.OrderedDict()  # session_key -> Session, least recently used first
+        self.last_session = None  # None: the per-call path ran; 'captured' / 'replayed': a session was built / reused by the last call
+        self.reuse_graph = _reuse_graph(reuse_graph)
+
+    def set_reuse_graph(self, flag=None):
+        """True: reverse_ddpm / reverse_ddpm_ensemble keep their captured step graph in a Session of the sde and replay it for every
+        later image of the same configuration (same bits; the sde then owns the graph's memory until close_sessions()).  False / None:
+        every call captures and frees its own graph, and the sessions held so far are closed."""
+        self.reuse_graph = _reuse_graph(flag)
+        if not self.reuse_graph:
+            self.close_sessions()
+
+    def close_sessions(self):
+        """drop every held step graph with its buffers and memory pool"""
+        while self._sessions:
+            self._sessions.popitem(last=False)[1].close()
+
+    def _hold_session(self, key, session):
+        """keep `session` as the most recently used one; beyond MAX_SESSIONS the least recently used are closed"""
+        self._sessions[key] = session
+        self._sessions.move_to_end(key)
+        while len(self._sessions) > MAX_SESSIONS:
+            self._sessions.popitem(last=False)[1].close()
 
     def set_interval(self, level=None):
         """credible level L in (0, 1) of the interval maps reverse_ddpm_ensemble leaves in last_order_stats (None: off).  Only
@@ -651,6 +736,121 @@ class driftSDE:
             ops.drift_reverse_step_tiled_dev(self.x, r_tiles, e_tiles, self.r_prev, self.e_prev, self.noises, self.cond, self.x_tiles,
                                              self.xa_tiles, self.plan, self.coef, self.state, self.sde.seed, self.nper, self.off_base)
 
+    class Session:
+        """A captured step graph that outlives the call: the buffers it is baked on, ONE ordinary Stepper over them, and strong
+        references to every tensor the graph reads without owning.
+          * x, xa, cond [rows, C, H, W], the context buffer, the int32 class-index buffer the nets take as `names` and, for a member
+            chain, the int64 member buffer are refilled per image by library launches and a few bytes of host-to-device copy.
+          * `held`: the nets' cache values after the warm step (MSM_degEmb_Unet.held_cache_values).  Several of those caches hold one
+            value and replace it when a call of another batch size or context comes through; the graph holds addresses.
+          * `vecs`: the single-token context vectors of the warm step.  The library refills the context buffer through raw pointers,
+            so the nets' cache key (ctx._version, identity) cannot see it: begin() recomputes every vector and copies it into the
+            tensor the graph reads.
+        start() serves the first image (warm step and capture, Stepper.prepare), begin() every later one; the caller then runs
+        stepper.run() and copies x out, since x belongs to the next image."""
+
+        def __init__(self, sde, key, rows, cond, image_context, members):
+            # the sde owns its sessions, so the session and its Stepper see the sde through a weak proxy: no reference cycle, and an
+            # sde that is dropped frees its graphs at once by reference count -- never at some later garbage collection, which
+            # could fall inside another chain's graph capture
+            self.sde, self.key = weakref.proxy(sde), key
+            dev = cond.device
+            shape = (rows,) + tuple(cond.shape[1:])
+            self.x, self.xa, self.cond = (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
+            self.ctx = None if image_context is None else torch.empty((rows,) + tuple(image_context.shape[1:]), dtype=torch.float32, device=dev)
+            self.idx = torch.zeros(rows, dtype=torch.int32, device=dev)
+            self.members = torch.ones(rows, dtype=torch.int64, device=dev) if members else None
+            self.stepper = None
+            self.held, self.vecs = [], []
+
+        def _fill(self, cond, idx, image_context, members, offset, calls0, S, row0):
+            """this image's inputs into the buffers; the chain's start and device state in one launch"""
+            st, sde = self.stepper, self.sde
+            self.idx.copy_(torch.tensor(idx, dtype=torch.int32))
+            if self.members is not None:
+                self.members.copy_(torch.tensor(members, dtype=torch.int64))
+            if self.ctx is not None:
+                ops.axpby(image_context, image_context, 1.0, 0.0, out=self.ctx)
+            ops.chain_begin(cond, self.cond, self.x, self.xa, st.state, st.tdev, sde.max_sigma, sde.seed, offset=offset,
+                            t0=st.t_first if st.next_t is not None else st.T, calls0=calls0, members=self.members, S=S, row0=row0)
+
+        def start(self, cond, idx, image_context, text_encoder, sched, order, T_stop, members=None, offset=0, S=1, row0=0):
+            """the first image: the Stepper on the buffers, the fill, then warm step and capture -> the steps executed (1)"""
+            self.stepper = driftSDE.Stepper(self.sde, self.x, self.cond, self.idx, text_encoder, self.ctx, t_stop=T_stop, timesteps=sched,
+                                            solver_order=order, members=self.members, xa=self.xa)
+            self._fill(cond, idx, image_context, members, offset, 0, S, row0)
+            done = self.stepper.prepare()
+            if self.stepper.graph:
+                for net in (self.sde.drift_net, self.sde.noise_net):
+                    core = _core(net)
+                    self.held.extend(core.held_cache_values())
+                    c = core._ctx_cache
+                    if self.ctx is not None and c is not None and c[2]() is self.ctx:
+                        self.vecs.extend((ca, c[1][id(ca)]) for ca in core.cross_attns())
+                self.held.append(text_encoder)
+            return done
+
+        def begin(self, cond, idx, image_context, members=None, offset=0, calls0=0, S=1, row0=0):
+            """a later image: refill the buffers, rewind the device state, refresh the context vectors the graph reads"""
+            self._fill(cond, idx, image_context, members, offset, calls0, S, row0)
+            for ca, held in self.vecs:
+                fresh = ca.single_token_vec(self.ctx)
+                ops.axpby(fresh, fresh, 1.0, 0.0, out=held)
+
+        def close(self):
+            self.stepper = self.x = self.xa = self.cond = self.ctx = self.idx = self.members = None
+            self.held, self.vecs = [], []
+
+    def _session_indices(self, names, cond, image_context, nsteps):
+        """the class indices of `names` when a session may serve the call, else None (the per-call path runs): reuse_graph on, a chain
+        that would capture (HIP graphs on, device tensors, at least 3 steps), fp32 inputs, and both nets UNets of this package in eval
+        mode that agree on the indices"""
+        if not (self.reuse_graph and self.hip_graph and cond.is_cuda and nsteps >= 3 and cond.dtype == torch.float32):
+            return None
+        if image_context is not None and (image_context.dtype != torch.float32 or image_context.device != cond.device):
+            return None
+        cores = [_core(self.drift_net), _core(self.noise_net)]
+        if not all(hasattr(c, "held_cache_values") and hasattr(c, "type_map_ind") and not getattr(c, "training", False) for c in cores):
+            return None
+        if torch.is_tensor(names) or any(n not in c.type_map_ind for c in cores for n in names):
+            return None
+        idx = [cores[0].type_map_ind[n] for n in names]
+        return idx if idx == [cores[1].type_map_ind[n] for n in names] else None
+
+    def _session_run(self, kind, cond, idx, text_encoder, image_context, sched, nsteps, order, T_stop, rows, members=None, S=1, row0=0):
+        """One chain of `rows` rows through a held session -> (the session's x -- which the next image overwrites --, its stepper,
+        'captured' | 'replayed'), or through a session that failed to capture and is dropped -> (x, stepper, None).  A plain chain's
+        x_T draw keeps the per-call accounting: one draw of the batch's size at the stream's position."""
+        key = session_key(self, kind, rows, cond.shape[1:], None if image_context is None else image_context.shape[1:], sched, order, T_stop,
+                          text_encoder, cond.device)
+        offset = nper = 0
+        if kind == "plain":
+            nper = (cond.numel() + 3) // 4
+            offset = self._off
+            self._calls += 1
+            self._off += nper
+        ses = self._sessions.get(key)
+        calls0 = 0
+        if ses is not None and kind == "plain":
+            calls0 = session_calls0(self._off, ses.stepper.off_base, nper, nsteps)
+            if calls0 is None:
+                self._sessions.pop(key).close()
+                ses = None
+        if ses is not None:
+            self._sessions.move_to_end(key)
+            ses.begin(cond, idx, image_context, members=members, offset=offset, calls0=calls0, S=S, row0=row0)
+            ses.stepper.run(nsteps)
+            return ses.x, ses.stepper, "replayed"
+        for stale in [k for k in self._sessions if k[:-1] == key[:-1]]:  # the same configuration on weights that have changed since
+            self._sessions.pop(stale).close()
+        ses = driftSDE.Session(self, key, rows, cond, image_context, kind == "member")
+        done = ses.start(cond, idx, image_context, text_encoder, sched, order, T_stop, members=members, offset=offset, S=S, row0=row0)
+        ses.stepper.run(nsteps - done)
+        if not ses.stepper.graph:
+            return ses.x, ses.stepper, None
+        self._hold_session(key, ses)
+        return ses.x, ses.stepper, "captured"
+
     def _chain_plan(self, reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm"):
         """-> (schedule or None, steps, solver order) of a reverse chain down to T_stop, after the option checks"""
         if optimize_type not in ("inputRes", "predict_noise", ""):
@@ -696,8 +896,15 @@ class driftSDE:
                                            image_context=image_context, x_T=x_T, noises=noises, T_stop=T_stop)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop)
         cond = cond.contiguous()
-        x = self._start_state(cond, x_T)
         self.last_tiles = None
+        self.last_session = None
+        idx = self._session_indices(names, cond, image_context, nsteps) if (x_T is None and noises is None) else None
+        if idx is not None:
+            ctx = None if image_context is None else image_context.contiguous()
+            x, stepper, self.last_session = self._session_run("plain", cond, idx, text_encoder, ctx, sched, nsteps, order, T_stop, cond.shape[0])
+            self._record_run(stepper, nsteps, order)
+            return ops.axpby(x, x, 1.0, 0.0)  # a copy by a library launch: the session's x is the next image's
+        x = self._start_state(cond, x_T)
         stepper = driftSDE.Stepper(self, x, cond, names, text_encoder, image_context, noises=noises, t_stop=T_stop, timesteps=sched,
                                    solver_order=order)
         out = stepper.run(nsteps)
@@ -723,6 +930,7 @@ class driftSDE:
         if W % 4:
             raise ValueError(f"reverse_ddpm_tiled: the image width {W} is not a multiple of 4")
         plan = self._tile_plan(H, W, cond.device)
+        self.last_session = None  # a tiled chain always captures per call
         x = self._start_state(cond, x_T)
         nwin = plan.ny * plan.nx
         names_rep = [n for n in names for _ in range(nwin)]
@@ -769,16 +977,30 @@ class driftSDE:
             raise ValueError(f"reverse_ddpm_ensemble: noises must be [steps, B*S = {R}, ...], got {tuple(noises.shape)}")
         ids = self._assign_members(B, S, members)
         mdev = ops.member_ids(ids, cond.device)
-        cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
         names_rep = [n for n in names for _ in range(S)]
         ctx_rep = None if image_context is None else image_context.repeat_interleave(S, dim=0)
-        for r0 in range(0, R, self.max_batch):
-            r1 = min(r0 + self.max_batch, R)
-            stepper = driftSDE.Stepper(self, x[r0:r1], cond_rep[r0:r1], names_rep[r0:r1], text_encoder,
-                                       None if ctx_rep is None else ctx_rep[r0:r1].contiguous(),
-                                       noises=None if noises is None else noises[:, r0:r1].contiguous(), t_stop=T_stop, timesteps=sched,
-                                       solver_order=order, members=mdev[r0:r1], xa=xa[r0:r1])
-            stepper.run(nsteps)
+        self.last_session = None
+        idx = self._session_indices(names_rep, cond, image_context, nsteps) if noises is None else None
+        if idx is not None:
+            # each chunk through the member session of its row count: a full chunk and a shorter last chunk are two sessions
+            x = torch.empty((R,) + tuple(cond.shape[1:]), dtype=torch.float32, device=cond.device)
+            how = []
+            for r0 in range(0, R, self.max_batch):
+                r1 = min(r0 + self.max_batch, R)
+                rows, stepper, state = self._session_run("member", cond, idx[r0:r1], text_encoder, None if ctx_rep is None else ctx_rep[r0:r1],
+                                                         sched, nsteps, order, T_stop, r1 - r0, members=ids[r0:r1], S=S, row0=r0)
+                ops.axpby(rows, rows, 1.0, 0.0, out=x[r0:r1])
+                how.append(state)
+            self.last_session = None if None in how else ("captured" if "captured" in how else "replayed")
+        else:
+            cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
+            for r0 in range(0, R, self.max_batch):
+                r1 = min(r0 + self.max_batch, R)
+                stepper = driftSDE.Stepper(self, x[r0:r1], cond_rep[r0:r1], names_rep[r0:r1], text_encoder,
+                                           None if ctx_rep is None else ctx_rep[r0:r1].contiguous(),
+                                           noises=None if noises is None else noises[:, r0:r1].contiguous(), t_stop=T_stop, timesteps=sched,
+                                           solver_order=order, members=mdev[r0:r1], xa=xa[r0:r1])
+                stepper.run(nsteps)
         self._record_run(stepper, nsteps, order)
         self.last_members = torch.tensor(ids, dtype=torch.int64).view(B, S)
         samples = x.view((B, S) + tuple(cond.shape[1:]))

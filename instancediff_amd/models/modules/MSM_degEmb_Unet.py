@@ -748,12 +748,34 @@ class LearnableForwardUNet_MultiScoreMap(nn.Module):
         return cas
 
     def class_index(self, names, device):
+        """class indices of `names` as int32 [B] on the device.  An int32 device tensor is taken as the indices themselves and returned
+        as it is: the owner of a held step graph rewrites that one tensor per image (driftSDE reuse_graph)."""
+        if torch.is_tensor(names):
+            if names.dtype != torch.int32 or names.dim() != 1 or names.device.type != torch.device(device).type:
+                raise ValueError(f"class_index: an index tensor must be int32 [B] on {device}, got {names.dtype} {tuple(names.shape)} on {names.device}")
+            return names
         key = (tuple(names), str(device))
         hit = self._idx_cache.get(key)
         if hit is None:
             hit = torch.tensor([self.type_map_ind[n] for n in names], dtype=torch.int32, device=device)
             self._idx_cache[key] = hit
         return hit
+
+    def held_cache_values(self):
+        """Every cached value the net's inference forward reads at this moment, as a list to keep alive: the prepared-weight entries
+        (_PREP) of the net's modules, each ScoreMapModule's text embedding, the single-token context vectors and the class-index
+        tensors.  Several of these caches hold ONE value and replace it when a call of another batch size or context comes through;
+        a captured step graph holds their addresses, not references, so its owner keeps this list for as long as it may replay."""
+        held = []
+        for mod in self.modules():
+            slot = _PREP.store.get(mod)
+            if slot:
+                held.extend(slot.values())
+        held.extend(m._text_cache for m in self.score_map_modules() if m._text_cache is not None)
+        if self._ctx_cache is not None:
+            held.append(self._ctx_cache[1])
+        held.extend(self._idx_cache.values())
+        return held
 
     def _films(self, temb):
         """all ResBlock time projections Linear(SiLU(temb)) in ONE launch -> per-block [B, 2C] views."""

@@ -850,6 +850,22 @@ def ensemble_init(cond, S, members, sigma, seed):
     return cond_rep, x, xa
 
 
+def chain_begin(cond_in, cond, x, xa, state, tdev, sigma, seed, offset=0, t0=0, calls0=0, members=None, S=1, row0=0):
+    """The start of an image in a held chain (idiff_chain_begin), one launch: cond <- cond_in's rows, x <- cond + sigma*z, xa <- x - cond,
+    state <- {t0, calls0, 0}, tdev[:] <- t0.  Plain chain (members None): cond_in and the outputs are [B, ...], z is randn(seed, offset)
+    over the flattened batch.  Member chain: cond_in is [B, ...], the outputs [R, ...] are rows row0 .. row0 + R of the B*S ensemble
+    rows, row r from member members[r] (int64 [R] on the device) at draw 0."""
+    lib = _lib.load()
+    _c(cond_in, "cond_in"), _c(cond, "cond"), _c(x, "x"), _c(xa, "xa"), _c(state, "state", torch.int32), _c(tdev, "tdev")
+    B, R = cond_in.shape[0], cond.shape[0]
+    n_s = cond_in.numel() // B
+    if state.numel() != 3 or tdev.numel() != R or x.shape != cond.shape or xa.shape != cond.shape or cond.numel() != R * n_s:
+        raise _lib.IdiffError(f"chain_begin: cond / x / xa must be [R, sample] alike, state int32 [3], tdev [R]; got {tuple(cond.shape)}, "
+                              f"{tuple(x.shape)}, {tuple(xa.shape)}, {tuple(state.shape)}, {tuple(tdev.shape)} for samples of {n_s}")
+    check(lib.idiff_chain_begin(_p(cond_in), _p(cond), _p(x), _p(xa), B, S, n_s, row0, R, None if members is None else _members(members, R),
+                                sigma, seed, offset, C.c_void_p(state.data_ptr()), _p(tdev), t0, calls0, _stream()), "chain_begin")
+
+
 def drift_reverse_step_members_dev(x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, coef, state, members, seed):
     """drift_reverse_step_dev (coef [3, T+1], r_prev = e_prev = None) or drift_reverse_step2_dev (coef [5, T+1]) on the rows of x
     [R, ...], with row r's z from member members[r]'s stream at draw 1 + state[1] (or from z_base [steps, R, ...])"""

@@ -10,7 +10,8 @@ an S-member posterior ensemble: the metrics and the triptych are the mean's, `PS
 With `--interval L` on top of that the per-pixel median and the level-L credible interval of the members are written as `<i>_median_` / `<i>_lo_` /
 `<i>_hi_WxHx1.raw` maps, and `PSNR_median`, `COVER` (the share of ground-truth pixels inside the interval) and `WIDTH` (its mean width) are listed.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
-full-resolution chain.  With `--random-init` the checkpoint load
+full-resolution chain.  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
+With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
@@ -48,6 +49,9 @@ def main(argv=None):
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
                         help="driftSDE tile_overlap: pixels shared by adjacent windows (default tile // 8; overrides the YAML)")
+    parser.add_argument("--reuse-graph", action="store_true",
+                        help="driftSDE reuse_graph: keep the captured step graph and replay it for every later image of the same shape "
+                             "(same bits; overrides the YAML)")
     args = parser.parse_args(argv)
     if args.tile is not None and len(args.tile) > 2:
         parser.error("--tile takes one size P or two, Ph Pw")
@@ -77,6 +81,8 @@ def main(argv=None):
         sde_opt['tile'] = args.tile[0] if len(args.tile) == 1 else list(args.tile)
     if args.tile_overlap is not None:
         sde_opt['tile_overlap'] = args.tile_overlap
+    if args.reuse_graph:
+        sde_opt['reuse_graph'] = True
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
@@ -92,7 +98,7 @@ def main(argv=None):
         for r in results.values():
             r['PSNR_median'], r['COVER'], r['WIDTH'] = [], [], []
     times = []
-    n_done = 0
+    n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
         if args.limit and n_done >= args.limit:
             break
@@ -112,6 +118,7 @@ def main(argv=None):
                 tic = time.time()
                 model.test(**({'return_samples': True} if S > 1 else {}))
                 times.append(time.time() - tic)
+                n_replayed += getattr(sde, 'last_session', None) == 'replayed'
                 rmse, psnr, ssim = ops.image_metrics(model.output[:, 0], model.target[:, 0]).cpu().tolist()[0]
                 r = results[it["name"]]
                 r['RMSE'].append(rmse), r['SSIM'].append(ssim), r['PSNR'].append(psnr)
@@ -150,7 +157,8 @@ def main(argv=None):
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
               + (f", {S} samples per image" if S > 1 else "")
               + ("" if level is None else f", interval {level} (nominal {sde.last_order_stats['nominal']})")
-              + ("" if getattr(sde, 'last_tiles', None) is None else ", {}x{} windows of {}x{}".format(*sde.last_tiles)))
+              + ("" if getattr(sde, 'last_tiles', None) is None else ", {}x{} windows of {}x{}".format(*sde.last_tiles))
+              + (f", graph reused for {n_replayed} of {len(times)} images" if getattr(sde, 'reuse_graph', False) else ""))
     if world > 1 and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return results
