@@ -704,6 +704,35 @@ int idiff_image_metrics(const float* pred, const float* target, float* out_b3, f
 int idiff_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, float grad_scale, int step, idiff_stream_t stream);
 
+/* Gradient-norm guard of the optimizer step (global-norm clipping as torch.nn.utils.clip_grad_norm_, and skipping a step whose
+ * gradient is not finite; the reference's loop has neither).  Three launches back to back on one stream, nothing read on the host.
+ *
+ * idiff_grad_sumsq: part[k] = sum of g[i]^2 over the elements workgroup k owns, k < P = idiff_grad_sumsq_parts() = 1024 (a fixed
+ * grid of P workgroups x 256 threads, four per CU).  A thread strides over the float4s of g with the whole grid, keeps one fp32
+ * accumulator per float4 lane and adds them as (x + y) + (z + w); wave sums, then the four wave sums through LDS as
+ * (w0 + w1) + (w2 + w3); the n % 4 tail elements go, one by one, to thread 0 of workgroup 0; a workgroup with no element writes 0.
+ * No atomics, nothing passed between workgroups: part is a function of (g, n) alone, bit-identical from run to run.
+ * g: 16-byte aligned; n >= 1.  A misaligned g, n < 1 or a null pointer: IDIFF_E_BADARG, nothing launched, part untouched. */
+int64_t idiff_grad_sumsq_parts(void);
+int idiff_grad_sumsq(const float* g, int64_t n, float* part /* [P] */, idiff_stream_t stream);
+/* idiff_grad_guard: one wave over the nbuf * P partials of nbuf >= 1 buffers (each buffer's idiff_grad_sumsq wrote its own range
+ * [b * P, (b + 1) * P) of part: one norm over all parameter groups).  Lane l adds part[l], part[l + 64], ... in index order in fp64,
+ * the 64 lane sums meet in a fixed butterfly: S.  info [4] on the device:
+ *   info[0] = norm    = (float)(|grad_scale| * sqrt(S)), in fp64, rounded once: the L2 norm of the gradient as idiff_adam_step scales it
+ *   info[1] = coef    = 1 if max_norm <= 0 (no clipping), else (float)min(1, max_norm / ((double)norm + 1e-6)): clip_grad_norm_ with
+ *                       error_if_nonfinite=False -- an inf norm gives 0, a NaN norm gives NaN
+ *   info[2] = applied = 0.0f if skip_nonfinite != 0 and norm is NaN or +-inf, else 1.0f.  The partials are fp32: a sum of squares
+ *                       that overflows fp32 (or a norm that overflows it) is inf and counts as non-finite
+ *   info[3] = 0 */
+int idiff_grad_guard(const float* part, int nbuf, float grad_scale, float max_norm, int skip_nonfinite, float* info /* [4] */,
+                     idiff_stream_t stream);
+/* idiff_adam_step with coef = info[1] and applied = info[2] read on the device (uniform over the grid).  applied == 0: every thread
+ * returns before it reads or writes p, m or v, which stay bit for bit as they were whatever g holds.  Otherwise the gradient is
+ * (g[i] * grad_scale) * coef and the rest is idiff_adam_step's update, the same device code; with coef == 1.0f the result is
+ * bit-identical to idiff_adam_step on the same operands.  info must not overlap p, g, m or v (IDIFF_E_BADARG). */
+int idiff_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, float grad_scale, int step, const float* info, idiff_stream_t stream);
+
 /* bf16 wire format of the data-parallel gradient exchange (replaces nothing in the reference, whose DDP buckets are fp32,
  * models/drift_noise_model.py:145-146; BASELINE config c3 asks for it): round-to-nearest-even pack of the flat fp32 gradient
  * buffer, and the widening unpack after the all-reduce.  The fp32 buffer stays the master copy Adam reads. */

@@ -181,6 +181,10 @@ SIGNATURES = {
     "idiff_f32_to_bf16": (I, [P, P, I64, c_stream]),
     "idiff_bf16_to_f32": (I, [P, P, I64, c_stream]),
     "idiff_adam_step": (I, [P, P, P, P, I64, F, F, F, F, F, F, I, c_stream]),
+    "idiff_grad_sumsq_parts": (I64, []),
+    "idiff_grad_sumsq": (I, [P, I64, P, c_stream]),
+    "idiff_grad_guard": (I, [P, I, F, F, I, P, c_stream]),
+    "idiff_adam_step_dev": (I, [P, P, P, P, I64, F, F, F, F, F, F, I, P, c_stream]),
 }
 
 

@@ -658,11 +658,21 @@ __global__ void sum_small_kernel(const float* __restrict__ part, int n, float sc
 }
 
 // Adam with L2-in-gradient weight decay (torch.optim.Adam, not AdamW), grad pre-scale (1/world for the flat
-// all-reduce), bias corrections folded into step_size / bc2_sqrt on the host
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
-                            float lr, float beta1, float beta2, float eps, float wd, float gscale, float bc1, float bc2_sqrt) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float gr = g[i] * gscale;
+// all-reduce), bias corrections folded into step_size / bc2_sqrt on the host.  The update is written ONCE, here: adam_kernel is
+// adam_update<false>, adam_dev_kernel (the guarded step) picks <false> or <true> by the clip coefficient it reads from the device.
+// a * b rounded to fp32 on its own: never contracted into a following add
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+// CLIP: the gradient is (g * gscale) * coef, the inner product rounded first (clip_grad_norm_ scales the already averaged gradient);
+// it enters the update in the same expression as the unclipped g * gscale does, so nothing behind it is arranged differently.
+template <bool CLIP>
+__device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            long long i0, long long stride, long long n, float lr, float beta1, float beta2, float eps,
+                                            float wd, float gscale, float coef, float bc1, float bc2_sqrt) {
+    for (long long i = i0; i < n; i += stride) {
+        float gr = CLIP ? mul_rounded(g[i], gscale) * coef : g[i] * gscale;
         const float pv = p[i];
         gr += wd * pv;
         const float mm = beta1 * m[i] + (1.f - beta1) * gr;
@@ -671,6 +681,66 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         v[i] = vv;
         const float denom = sqrtf(vv) / bc2_sqrt + eps;
         p[i] = pv - (lr / bc1) * (mm / denom);
+    }
+}
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
+                            float lr, float beta1, float beta2, float eps, float wd, float gscale, float bc1, float bc2_sqrt) {
+    adam_update<false>(p, g, m, v, blockIdx.x * (long long)blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x, n, lr, beta1, beta2, eps, wd,
+                       gscale, 1.f, bc1, bc2_sqrt);
+}
+// The guarded step: info = idiff_grad_guard's record, {norm, coef, applied, 0}, uniform over the grid.  applied == 0: every thread
+// returns before it touches p, m or v.  coef == 1 (not clipped, the usual step): adam_kernel's own instantiation, so its bits.
+__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
+                                float lr, float beta1, float beta2, float eps, float wd, float gscale, float bc1, float bc2_sqrt,
+                                const float* __restrict__ info) {
+    const float coef = info[1];
+    if (info[2] == 0.f) return;
+    const long long i0 = blockIdx.x * (long long)blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    if (coef == 1.f)
+        adam_update<false>(p, g, m, v, i0, stride, n, lr, beta1, beta2, eps, wd, gscale, 1.f, bc1, bc2_sqrt);
+    else
+        adam_update<true>(p, g, m, v, i0, stride, n, lr, beta1, beta2, eps, wd, gscale, coef, bc1, bc2_sqrt);
+}
+
+// ---- gradient-norm guard: sum of squares of a flat buffer as IDIFF_GRAD_PARTS block partials (fixed grid, fixed order, no atomics, no
+// traffic between workgroups: a function of (g, n) alone), then one wave that turns the partials of all buffers into {norm, coef, applied}.
+#define IDIFF_GRAD_PARTS 1024  // 4 workgroups of 256 threads on each of the 256 CUs
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, float* __restrict__ part, long long n) {
+    __shared__ float red[4];
+    const long long n4 = n >> 2;
+    const floatx4* g4 = reinterpret_cast<const floatx4*>(g);
+    floatx4 a = {0.f, 0.f, 0.f, 0.f};
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const floatx4 x = g4[i];
+        a.x += x.x * x.x, a.y += x.y * x.y, a.z += x.z * x.z, a.w += x.w * x.w;
+    }
+    float s = (a.x + a.y) + (a.z + a.w);
+    if (blockIdx.x == 0 && threadIdx.x == 0)  // the n % 4 elements behind the last float4
+        for (long long i = n4 << 2; i < n; ++i) s += g[i] * g[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// one wave: lane l adds part[l], part[l + 64], ... in index order in fp64, the 64 lane sums meet in the butterfly's fixed order
+__global__ __launch_bounds__(64) void grad_guard_kernel(const float* __restrict__ part, int count, float gscale, float max_norm, int skip_nonfinite,
+                                                        float* __restrict__ info) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < count; i += 64) s += (double)part[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) {
+        const float norm = (float)(fabs((double)gscale) * sqrt(s));
+        float coef = 1.f;
+        if (!(max_norm <= 0.f)) {  // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1); inf -> 0, NaN -> NaN
+            const double c = (double)max_norm / ((double)norm + 1e-6);
+            coef = (float)(c > 1.0 ? 1.0 : c);
+        }
+        const bool finite = fabsf(norm) <= 3.402823466e+38f;  // false for NaN and +-inf
+        info[0] = norm;
+        info[1] = coef;
+        info[2] = (skip_nonfinite && !finite) ? 0.f : 1.f;
+        info[3] = 0.f;
     }
 }
 
@@ -896,6 +966,38 @@ extern "C" int idiff_adam_step(float* p, const float* g, float* m, float* v, int
     hipLaunchKernelGGL(adam_kernel, dim3(bgrid(n, 256, 8192)), dim3(256), 0, ST, p, g, m, v, (long long)n, lr, beta1, beta2, eps, weight_decay,
                        grad_scale, bc1, bc2_sqrt);
     IDIFF_CHECK_LAUNCH("adam_step");
+    return IDIFF_OK;
+}
+extern "C" int64_t idiff_grad_sumsq_parts(void) { return IDIFF_GRAD_PARTS; }
+extern "C" int idiff_grad_sumsq(const float* g, int64_t n, float* part, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(g && part && n > 0 && ((uintptr_t)g & 15) == 0, "grad_sumsq: bad args (g must be 16-byte aligned, n >= 1)");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(IDIFF_GRAD_PARTS), dim3(256), 0, ST, g, part, (long long)n);
+    IDIFF_CHECK_LAUNCH("grad_sumsq");
+    return IDIFF_OK;
+}
+extern "C" int idiff_grad_guard(const float* part, int nbuf, float grad_scale, float max_norm, int skip_nonfinite, float* info,
+                                idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(part && info && nbuf >= 1 && nbuf <= (1 << 20), "grad_guard: bad args");
+    hipLaunchKernelGGL(grad_guard_kernel, dim3(1), dim3(64), 0, ST, part, nbuf * IDIFF_GRAD_PARTS, grad_scale, max_norm, skip_nonfinite, info);
+    IDIFF_CHECK_LAUNCH("grad_guard");
+    return IDIFF_OK;
+}
+// [a, a + na) and [b, b + nb) bytes share no byte
+static bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x + na <= y || y + nb <= x;
+}
+extern "C" int idiff_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, float grad_scale, int step, const float* info, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(p && g && m && v && info && n > 0 && step >= 1, "adam_step_dev: bad args");
+    const size_t nb = (size_t)n * sizeof(float), ni = 4 * sizeof(float);
+    IDIFF_CHECK_ARG(disjoint(info, ni, p, nb) && disjoint(info, ni, g, nb) && disjoint(info, ni, m, nb) && disjoint(info, ni, v, nb),
+                    "adam_step_dev: info aliases p, g, m or v");
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(bgrid(n, 256, 8192)), dim3(256), 0, ST, p, g, m, v, (long long)n, lr, beta1, beta2, eps, weight_decay,
+                       grad_scale, bc1, bc2_sqrt, info);
+    IDIFF_CHECK_LAUNCH("adam_step_dev");
     return IDIFF_OK;
 }
 

@@ -80,7 +80,8 @@ class CLIPDriftModel():
                  dist=False, gpu=True, optimize_type='predict_noise', optimize_target='std', if_train=True, dnet_settings=None,
                  nnet_settings=None, drift_loss='l2', noise_loss='none', if_MultiScoreMap=False, score_map_ch_mult=[1, 1, 2, 4],
                  score_map_ngf=64, use_image_context=False, use_degra_context=False, CLIP_Type="CLIP", device=None, text_encoder=None,
-                 class_tokens=None, score_map_dropout=0.1, score_map_decoder="ContextDecoder", score_map_if_flash=False, conv_dtype="f32"):
+                 class_tokens=None, score_map_dropout=0.1, score_map_decoder="ContextDecoder", score_map_if_flash=False, conv_dtype="f32",
+                 grad_clip_norm=None, skip_nonfinite_steps=False):
         """score_map_dropout: dropout of the ScoreMapModules' decoder blocks in training mode -- the reference builds them with
         ContextDecoder's default 0.1 (models/_modified_BiomedCLIP.py:1194-1201; drift_noise_model.py:110-112 passes no value);
         model option `score_map_dropout` overrides (0 = the deterministic training function of rounds 1-2).
@@ -91,8 +92,15 @@ class CLIPDriftModel():
         fp32, what if_flash=False computes.
         conv_dtype: operand precision of both nets' 3x3 convs, sampling and training -- "f32" (default, the parity path) or "bf16",
         the labelled reduced-precision variant (operands and weights rounded once to bf16 after the fp32 gather, fp32 sums and epilogue;
-        csrc/conv_bf16.hip); model option of the same name.  Anything else raises ValueError."""
+        csrc/conv_bf16.hip); model option of the same name.  Anything else raises ValueError.
+        grad_clip_norm (a finite number > 0, or None) / skip_nonfinite_steps (bool): the gradient guard of both optimizers (FusedAdam's
+        max_grad_norm / skip_nonfinite, each net clipped by its own global norm); model options of the same names.  Both off (the
+        default): the training step launches what it always launched."""
         conv_dtype = parse_conv_dtype(conv_dtype)
+        from ..train_ops import parse_max_grad_norm, parse_skip_nonfinite
+        self.grad_clip_norm = parse_max_grad_norm(grad_clip_norm, "grad_clip_norm")
+        self.skip_nonfinite_steps = parse_skip_nonfinite(skip_nonfinite_steps, "skip_nonfinite_steps")
+        self.grad_info, self.skipped_steps = None, 0
         dnet_settings = dict(dnet_settings)
         nnet_settings = dict(nnet_settings)
         for s in (dnet_settings, nnet_settings):  # :58-61
@@ -153,8 +161,9 @@ class CLIPDriftModel():
             self.grad_sync.broadcast_parameters(list(self.drift_net.parameters()) + list(self.noise_net.parameters()))
         if if_train:
             from ..train_ops import FusedAdam
-            self.drift_optimizer = FusedAdam(self.drift_net.parameters(), lr=drift_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2))
-            self.noise_optimizer = FusedAdam(self.noise_net.parameters(), lr=noise_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2))
+            guard = dict(max_grad_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite_steps)
+            self.drift_optimizer = FusedAdam(self.drift_net.parameters(), lr=drift_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2), **guard)
+            self.noise_optimizer = FusedAdam(self.noise_net.parameters(), lr=noise_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2), **guard)
             self.drift_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.drift_optimizer, T_max=nepoch, eta_min=eta_min)
             self.noise_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.noise_optimizer, T_max=nepoch, eta_min=eta_min)
         self.visuals = None
@@ -189,6 +198,18 @@ class CLIPDriftModel():
         for k in self.loss_info['latest'].keys():
             message += '({}={:4f}/{:4f})'.format(k, self.loss_info['latest'][k], self.loss_info['avg'][k] / num)
         return message
+
+    def get_grad_message(self):
+        """the gradient guard's line for the log: both nets' gradient norms and clip coefficients of the latest step and the running
+        count of skipped steps; empty until a guarded step has run"""
+        gi = self.grad_info
+        if not gi:
+            return ""
+        message = ""
+        for k, key in (('d', 'drift'), ('n', 'noise')):
+            if gi[key] is not None:
+                message += '({}gn={:.4e} {}coef={:.4f})'.format(k, gi[key]['norm'], k, gi[key]['coef'])
+        return message + '(skipped={:d})'.format(gi['skipped_steps'])
 
     def optimize_parameters(self):  # :231-232
         return self.optimize_parameters_inputRes()
@@ -324,6 +345,8 @@ class CLIPDriftModel():
                 opt.load_torch_adam(s)
             else:
                 opt.load_state_dict(s)
+        # iterations with a skipped step: the state holds one count per optimizer, and the larger is the most that is known of both
+        self.skipped_steps = max(self.drift_optimizer.skipped_steps, self.noise_optimizer.skipped_steps)
 
     @staticmethod
     def load_network(load_path, network, strict=True):
@@ -402,5 +425,9 @@ def create_CLIPDriftModel(train_opt, model_opt, phase='train', **extra):  # :758
         kw.update(score_map_if_flash=bool(model_opt['score_map_if_flash']))
     if model_opt.get('conv_dtype') is not None:
         kw.update(conv_dtype=parse_conv_dtype(model_opt['conv_dtype']))
+    if model_opt.get('grad_clip_norm') is not None:
+        kw.update(grad_clip_norm=model_opt['grad_clip_norm'])
+    if model_opt.get('skip_nonfinite_steps') is not None:
+        kw.update(skip_nonfinite_steps=model_opt['skip_nonfinite_steps'])
     kw.update(extra)
     return CLIPDriftModel(model_opt['text_encoder_pretrain_path'], **kw)

@@ -17,12 +17,14 @@ def load_options(path=DEFAULT_YAML, is_train=False):
 
 
 def build(opt=None, phase="test", device=None, T=None, seed=0, dist=False, sde_overrides=None, score_map_dropout=None, score_map_decoder=None, score_map_if_flash=None,
-          conv_dtype=None):
+          conv_dtype=None, grad_clip_norm=None, skip_nonfinite_steps=None):
     """-> (model: CLIPDriftModel, sde).  Random-init weights (seed) as the reference does for a fresh run.
     score_map_dropout: overrides the model option of that name (training-mode dropout of the ScoreMapModule decoder blocks; 0.1).
     score_map_decoder: overrides the model option of that name ("ContextDecoder" | "ContextDecoder_Hierachical").
     score_map_if_flash: overrides the model option of that name (the fp16 form of the Hierachical decoder's attentions).
-    conv_dtype: overrides the model option of that name ("f32" | "bf16": the operand precision of the 3x3 convs)."""
+    conv_dtype: overrides the model option of that name ("f32" | "bf16": the operand precision of the 3x3 convs).
+    grad_clip_norm / skip_nonfinite_steps: override the model options of those names (the training step's gradient guard: clip each net's
+    gradient to that global L2 norm; leave out a step whose gradient is not finite)."""
     opt = opt or load_options()
     train_opt = copy.deepcopy(dict(opt['train']))
     train_opt['dist'] = dist
@@ -40,6 +42,12 @@ def build(opt=None, phase="test", device=None, T=None, seed=0, dist=False, sde_o
     if conv_dtype is not None:
         model_opt = copy.copy(model_opt)
         model_opt['conv_dtype'] = conv_dtype
+    if grad_clip_norm is not None:
+        model_opt = copy.copy(model_opt)
+        model_opt['grad_clip_norm'] = grad_clip_norm
+    if skip_nonfinite_steps is not None:
+        model_opt = copy.copy(model_opt)
+        model_opt['skip_nonfinite_steps'] = skip_nonfinite_steps
     torch.manual_seed(seed)
     from .models.drift_noise_model import create_CLIPDriftModel  # registry target, imported for the device kwarg
     model = create_CLIPDriftModel(train_opt, model_opt, phase=phase, device=device) if device is not None else \

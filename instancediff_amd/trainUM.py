@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Training driver with the reference's CLI and option surface (trainUM.py:81-359):
 
-    python -m instancediff_amd.trainUM -opt <yaml> [--launcher none|pytorch] [--local_rank N]
+    python -m instancediff_amd.trainUM -opt <yaml> [--launcher none|pytorch] [--local_rank N] [--grad-clip-norm C] [--skip-nonfinite-steps]
     python -m torch.distributed.run --nproc-per-node N -m instancediff_amd.trainUM -opt <yaml> --launcher pytorch
 
 Differences from the reference (all in SURVEY.md §2.1/§3.1): world size comes from the environment (the
 reference hard-codes 2, :66); one flat RCCL gradient all-reduce per optimizer per step instead of 10 DDP wrappers;
 validation metrics (RMSE/PSNR/SSIM, :314-329) are computed on the device by one kernel; `max_iters` (optional
-key under `train:`) bounds a run for smoke tests.
+key under `train:`) bounds a run for smoke tests; `--grad-clip-norm` / `--skip-nonfinite-steps` (model options grad_clip_norm /
+skip_nonfinite_steps) switch on the gradient guard, whose norms, coefficients and skip count are then appended to the printed line.
 """
 import argparse
 import math
@@ -53,13 +54,31 @@ def validate(model, val_set, out_dir, limit=10):
     return acc / max(n, 1)
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-opt", type=str, help="Path to option YAML file.")
     parser.add_argument("--launcher", choices=["none", "pytorch"], default="none", help="job launcher")
     parser.add_argument("--local_rank", type=int, default=0)
-    args = parser.parse_args(argv)
-    opt = option.dict_to_nonedict(option.parse(args.opt, is_train=True))
+    parser.add_argument("--grad-clip-norm", type=float, default=None, metavar="C",
+                        help="clip each net's gradient to this global L2 norm (overrides the model option grad_clip_norm)")
+    parser.add_argument("--skip-nonfinite-steps", action="store_true",
+                        help="leave out an optimizer step whose gradient is NaN or inf (overrides the model option skip_nonfinite_steps)")
+    return parser
+
+
+def apply_model_overrides(opt, args):
+    """the command line's gradient-guard switches -> the options of the model that train.which_model names"""
+    model_opt = opt["models"][opt["train"]["which_model"]]
+    if args.grad_clip_norm is not None:
+        model_opt["grad_clip_norm"] = args.grad_clip_norm
+    if args.skip_nonfinite_steps:
+        model_opt["skip_nonfinite_steps"] = True
+    return opt
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    opt = apply_model_overrides(option.dict_to_nonedict(option.parse(args.opt, is_train=True)), args)
     set_seed(opt["train"]["manual_seed"])
     if args.launcher == "none":
         opt["dist"] = False
@@ -119,6 +138,7 @@ def main(argv=None):
             loss, dur = model.optimize_parameters()
             message = "<epoch:{:3d}, iter:{:8,d}, lr:{:.3e}> (fwd time {:.4f}) ".format(epoch, current_step, model.get_current_learning_rate(), dur)
             message += model.get_loss_message()
+            message += model.get_grad_message()  # empty unless grad_clip_norm / skip_nonfinite_steps is on
             if current_step % opt["logger"]["print_freq"] == 0 and rank <= 0:
                 print(message)
             if current_step % opt["logger"]["save_checkpoint_freq"] == 0 and rank <= 0:

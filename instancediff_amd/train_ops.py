@@ -1213,13 +1213,41 @@ def mse_loss_and_grad(pred, target, loss_slot, weight=1.0, want_grad=True):
     return grad
 
 
+def parse_max_grad_norm(value, name="max_grad_norm"):
+    """a finite float or int > 0, as a float, or None (off); bools, strings, 0, negatives, NaN and inf are refused"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0 < value < float("inf")):
+        raise ValueError(f"{name} must be a finite number > 0 (or None: off), got {value!r}")
+    return float(value)
+
+
+def parse_skip_nonfinite(value, name="skip_nonfinite"):
+    """a bool and nothing else (no 0 / 1, no strings)"""
+    if not isinstance(value, bool):
+        raise ValueError(f"{name} must be a bool, got {value!r}")
+    return value
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (L2 weight decay added to the gradient; config.yml:138-143) in ONE kernel launch per
     parameter group: parameters, gradients and both moments live in flat buffers (the parameters' .data / .grad are
-    views into them), so the flat RCCL all-reduce buffer, the Adam update and the 1/world gradient scale fuse."""
+    views into them), so the flat RCCL all-reduce buffer, the Adam update and the 1/world gradient scale fuse.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    The gradient guard (both options off by default, and step() is then the plain step, launch for launch):
+    max_grad_norm: clip the step's gradient to this global L2 norm, taken over all parameter groups of this optimizer after the
+        grad_scale -- torch.nn.utils.clip_grad_norm_(params, max_grad_norm) in front of torch.optim.Adam.
+    skip_nonfinite: a step whose gradient norm is NaN or inf leaves parameters and moments untouched, and does not count.
+    Norm, coefficient and the applied flag stay on the device (last_info, 4 floats: idiff_grad_guard's record); step() reads nothing
+    back.  settle() tells the host-side step count about a skipped step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+        max_grad_norm, skip_nonfinite = parse_max_grad_norm(max_grad_norm), parse_skip_nonfinite(skip_nonfinite)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, skip_nonfinite
+        self.last_info = self._part = None  # device buffers of the guard, allocated by the first guarded step
+        self.skipped_steps = 0
+        self._unsettled = False
         self._flat = []
         for group in self.param_groups:
             ps = [p for p in group['params'] if p.requires_grad]
@@ -1240,6 +1268,17 @@ class FusedAdam(torch.optim.Optimizer):
             self._flat.append(dict(p=fp, g=fg, m=torch.zeros_like(fp), v=torch.zeros_like(fp), step=0, params=ps))
         self.grad_scale = 1.0
         WEIGHT_EPOCH[0] += 1
+
+    def set_grad_guard(self, max_grad_norm=None, skip_nonfinite=False):
+        """switch the gradient guard (see the class); both off restores the plain step, which settles nothing: a guarded step still
+        open is settled here"""
+        max_grad_norm, skip_nonfinite = parse_max_grad_norm(max_grad_norm), parse_skip_nonfinite(skip_nonfinite)
+        self.settle()
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, skip_nonfinite
+
+    @property
+    def guarded(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
 
     def flat_grads(self):
         """the flat gradient buffers, complete: gradients autograd left in tensors of their own are gathered first (one launch)"""
@@ -1327,6 +1366,8 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.guarded:
+            return self._guarded_step()
         lib = _lib.load()
         self._collect()
         for group, f in zip(self.param_groups, self._flat):
@@ -1338,9 +1379,59 @@ class FusedAdam(torch.optim.Optimizer):
                                       group['weight_decay'], self.grad_scale, f['step'], _stream()), "adam_step")
         WEIGHT_EPOCH[0] += 1
 
+    def _guarded_step(self):
+        """sum of squares per group -> one guard launch over all groups' partials -> one device-scaled Adam launch per group, back
+        to back on the current stream.  f['step'] advances as in the plain step (the host-side bias corrections need it before the
+        device knows whether the step applies); settle() takes it back for a skipped step."""
+        lib = _lib.load()
+        self._collect()
+        if self._unsettled:  # nobody settled the previous step: fetch its record ourselves (one small copy)
+            self.settle()
+        live = [(group, f) for group, f in zip(self.param_groups, self._flat) if f is not None]
+        if not live:
+            return
+        parts = int(lib.idiff_grad_sumsq_parts())
+        if self._part is None or self._part.numel() != len(live) * parts:
+            dev = live[0][1]['g'].device
+            self._part = torch.zeros(len(live) * parts, device=dev, dtype=torch.float32)
+            if self.last_info is None:
+                self.last_info = torch.zeros(4, device=dev, dtype=torch.float32)
+        for k, (_, f) in enumerate(live):
+            check(lib.idiff_grad_sumsq(_p(f['g']), f['g'].numel(), self._part.data_ptr() + 4 * k * parts, _stream()), "grad_sumsq")
+        check(lib.idiff_grad_guard(_p(self._part), len(live), self.grad_scale, self.max_grad_norm or 0.0, int(self.skip_nonfinite),
+                                   _p(self.last_info), _stream()), "grad_guard")
+        for group, f in live:
+            f['step'] += 1
+            b1, b2 = group['betas']
+            check(lib.idiff_adam_step_dev(_p(f['p']), _p(f['g']), _p(f['m']), _p(f['v']), f['p'].numel(), group['lr'], b1, b2, group['eps'],
+                                          group['weight_decay'], self.grad_scale, f['step'], _p(self.last_info), _stream()), "adam_step_dev")
+        self._unsettled = True
+        WEIGHT_EPOCH[0] += 1
+
+    def settle(self, info_host=None):
+        """Close the last guarded step on the host: info_host = its record {norm, coef, applied, 0} as four host floats (the train step
+        passes the copy it makes anyway); None: fetched from last_info with one small synchronising copy, and nothing happens when no
+        guarded step is open.  A step that was not applied is taken back from every group's step count -- as with torch.optim, which
+        never sees a skipped step -- and counted in skipped_steps.  -> True when the step was skipped."""
+        if info_host is None:
+            if not self._unsettled:
+                return False
+            info_host = self.last_info.cpu().tolist()
+        self._unsettled = False
+        if float(info_host[2]) != 0.0:
+            return False
+        for f in self._flat:
+            if f is not None:
+                f['step'] -= 1
+        self.skipped_steps += 1
+        return True
+
     def state_dict(self):
+        if self._unsettled:
+            self.settle()
         sd = super().state_dict()
-        sd['flat'] = [None if f is None else dict(m=f['m'].cpu(), v=f['v'].cpu(), step=f['step']) for f in self._flat]
+        sd['flat'] = [None if f is None else dict(m=f['m'].cpu(), v=f['v'].cpu(), step=f['step'], skipped=self.skipped_steps)
+                      for f in self._flat]
         return sd
 
     def load_torch_adam(self, opt_or_state):
@@ -1384,6 +1475,8 @@ class FusedAdam(torch.optim.Optimizer):
                     f['m'].copy_(s['m'])
                     f['v'].copy_(s['v'])
                     f['step'] = s['step']
+                    self.skipped_steps = int(s.get('skipped', 0))  # older state files carry no count
+            self._unsettled = False
 
 
 def score_map_losses(score_maps, label, loss_rec, slot0, mult=(1, 2, 4, 8), size=None, want_grad=True):
@@ -1484,7 +1577,9 @@ def forward_backward_inputRes(model):
 
 def train_step_inputRes(model):
     """One optimisation step (drift_noise_model.py:242-312): forward_backward_inputRes, the data-parallel gradient exchange,
-    two Adam steps, loss bookkeeping with ONE device->host copy."""
+    two Adam steps, loss bookkeeping with ONE device->host copy.  With a gradient guard on (FusedAdam: max_grad_norm / skip_nonfinite) the
+    same copy brings both optimizers' {norm, coef, applied} records: model.grad_info = {'drift' / 'noise': {'norm', 'coef', 'skipped'},
+    'skipped_steps': iterations so far in which a step was skipped}.  The EMAs update after a skipped step too (harmless)."""
     m = model
     rec, iter_time, use_dsm, use_nsm = forward_backward_inputRes(m)
     scale = m.grad_sync.finish() if m.grad_sync is not None else 1.0  # the exchanges were started during the backward
@@ -1494,7 +1589,18 @@ def train_step_inputRes(model):
     for ema in (getattr(m, "dp_ema", None), getattr(m, "np_ema", None), m.dn_ema, m.nn_ema):
         if ema is not None:  # the reference builds the EMA objects but never calls update()
             ema.update()
+    guards = [(key, o) for key, o in (('drift', m.drift_optimizer), ('noise', m.noise_optimizer)) if o.guarded]
+    if guards:  # the guards' records ride on the loss record's copy (one launch stages them behind it)
+        rec = torch.cat([rec] + [o.last_info for _, o in guards])
     r = rec.cpu()  # the step's single device->host synchronisation (the reference does nine .item() calls)
+    if guards:
+        gi = {'drift': None, 'noise': None}
+        for j, (key, o) in enumerate(guards):
+            info = r[10 + 4 * j:14 + 4 * j].tolist()
+            gi[key] = {'norm': info[0], 'coef': info[1], 'skipped': o.settle(info)}
+        m.skipped_steps += any(g is not None and g['skipped'] for g in (gi['drift'], gi['noise']))
+        gi['skipped_steps'] = m.skipped_steps
+        m.grad_info = gi
     dl, nl = float(r[0]), float(r[1])
     dsml = float(r[2:6].sum()) / 2.0 if use_dsm else 0.0
     nsml = float(r[6:10].sum()) / 2.0 if use_nsm else 0.0
