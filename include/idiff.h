@@ -595,6 +595,11 @@ int idiff_sum_n(const float* const* srcs, const int64_t* src_bstrides, int nsrc,
  * array of nseg records {const float* src (NULL = zero fill); int64 dst_offset; int64 n; int64 first_block}, first_block = running
  * sum of ceil(n / 4096), ascending; nblocks = its total. */
 int idiff_gather_segments(const void* segs_dev, int nseg, int64_t nblocks, float* dst, idiff_stream_t stream);
+/* The accumulating form, for gradient accumulation (FusedAdam accum_steps > 1: micro-batches 2..k of a group): same table, same
+ * block mapping, dst[dst_offset + i] = dst[dst_offset + i] + src[i] -- one fp32 add, each element owned by one thread (no atomics:
+ * the result is a function of the operands alone).  A record with src == NULL leaves its range of dst untouched (the assigning
+ * entry point zero-fills it); so does everything between the records. */
+int idiff_gather_segments_acc(const void* segs_dev, int nseg, int64_t nblocks, float* dst, idiff_stream_t stream);
 /* forward marginals with per-sample coefficients (training-state samplers):
  *   out[b,:] = c0[b]*x0[b,:] + c1[b]*cond[b,:] + c2[b]*eps[b,:]      (driftSDE.forward_diffusion, IRSDE.generate_random_states) */
 int idiff_mix3_per_sample(const float* x0, const float* cond, const float* eps, const float* c0, const float* c1,

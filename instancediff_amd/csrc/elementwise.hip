@@ -641,17 +641,23 @@ struct idiff_gather_seg {
     long long n;
     long long blk0;
 };
-__global__ __launch_bounds__(256) void gather_segments_kernel(const idiff_gather_seg* __restrict__ segs, int nseg, float* __restrict__ dst) {
+// the segment of workgroup `blk` and its element range [i0, i1) inside it
+__device__ __forceinline__ idiff_gather_seg gather_seg_of_block(const idiff_gather_seg* __restrict__ segs, int nseg, long long blk, long long& i0,
+                                                                long long& i1) {
     int lo = 0, hi = nseg - 1;
-    const long long blk = blockIdx.x;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (segs[mid].blk0 <= blk) lo = mid;
         else hi = mid - 1;
     }
     const idiff_gather_seg sg = segs[lo];
-    const long long i0 = (blk - sg.blk0) * 4096;
-    const long long i1 = i0 + 4096 < sg.n ? i0 + 4096 : sg.n;
+    i0 = (blk - sg.blk0) * 4096;
+    i1 = i0 + 4096 < sg.n ? i0 + 4096 : sg.n;
+    return sg;
+}
+__global__ __launch_bounds__(256) void gather_segments_kernel(const idiff_gather_seg* __restrict__ segs, int nseg, float* __restrict__ dst) {
+    long long i0, i1;
+    const idiff_gather_seg sg = gather_seg_of_block(segs, nseg, blockIdx.x, i0, i1);
     float* d = dst + sg.dst;
     if (sg.src) {
         for (long long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = sg.src[i];
@@ -659,9 +665,24 @@ __global__ __launch_bounds__(256) void gather_segments_kernel(const idiff_gather
         for (long long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = 0.f;
     }
 }
+// The accumulating form (gradient accumulation: micro-batch 2..k of a group): dst += src, one fp32 add per element, every element
+// owned by one thread.  A record without a source leaves its range as it is (the parameter received no gradient in this micro-batch).
+__global__ __launch_bounds__(256) void gather_segments_acc_kernel(const idiff_gather_seg* __restrict__ segs, int nseg, float* __restrict__ dst) {
+    long long i0, i1;
+    const idiff_gather_seg sg = gather_seg_of_block(segs, nseg, blockIdx.x, i0, i1);
+    if (!sg.src) return;
+    float* d = dst + sg.dst;
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = __fadd_rn(d[i], sg.src[i]);
+}
 extern "C" int idiff_gather_segments(const void* segs_dev, int nseg, int64_t nblocks, float* dst, idiff_stream_t stream) {
     IDIFF_CHECK_ARG(segs_dev && dst && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31), "gather_segments: bad args");
     hipLaunchKernelGGL(gather_segments_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, static_cast<const idiff_gather_seg*>(segs_dev), nseg, dst);
     IDIFF_CHECK_LAUNCH("gather_segments");
+    return IDIFF_OK;
+}
+extern "C" int idiff_gather_segments_acc(const void* segs_dev, int nseg, int64_t nblocks, float* dst, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(segs_dev && dst && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31), "gather_segments_acc: bad args");
+    hipLaunchKernelGGL(gather_segments_acc_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, static_cast<const idiff_gather_seg*>(segs_dev), nseg, dst);
+    IDIFF_CHECK_LAUNCH("gather_segments_acc");
     return IDIFF_OK;
 }

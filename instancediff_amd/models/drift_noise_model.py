@@ -81,7 +81,7 @@ class CLIPDriftModel():
                  nnet_settings=None, drift_loss='l2', noise_loss='none', if_MultiScoreMap=False, score_map_ch_mult=[1, 1, 2, 4],
                  score_map_ngf=64, use_image_context=False, use_degra_context=False, CLIP_Type="CLIP", device=None, text_encoder=None,
                  class_tokens=None, score_map_dropout=0.1, score_map_decoder="ContextDecoder", score_map_if_flash=False, conv_dtype="f32",
-                 grad_clip_norm=None, skip_nonfinite_steps=False):
+                 grad_clip_norm=None, skip_nonfinite_steps=False, accum_steps=1):
         """score_map_dropout: dropout of the ScoreMapModules' decoder blocks in training mode -- the reference builds them with
         ContextDecoder's default 0.1 (models/_modified_BiomedCLIP.py:1194-1201; drift_noise_model.py:110-112 passes no value);
         model option `score_map_dropout` overrides (0 = the deterministic training function of rounds 1-2).
@@ -95,9 +95,15 @@ class CLIPDriftModel():
         csrc/conv_bf16.hip); model option of the same name.  Anything else raises ValueError.
         grad_clip_norm (a finite number > 0, or None) / skip_nonfinite_steps (bool): the gradient guard of both optimizers (FusedAdam's
         max_grad_norm / skip_nonfinite, each net clipped by its own global norm); model options of the same names.  Both off (the
-        default): the training step launches what it always launched."""
+        default): the training step launches what it always launched.
+        accum_steps (an int >= 1): gradient accumulation; model option of the same name.  Every optimize_parameters() is a micro-step on
+        the fed batch; the accum_steps-th of a group exchanges, applies both Adam steps to the mean of the group's gradients (equal
+        micro-batch sizes assumed), updates the EMAs and copies the group's mean losses to the host -- `stepped` says whether the last
+        call did.  1 (the default): every call is a step, as always."""
         conv_dtype = parse_conv_dtype(conv_dtype)
-        from ..train_ops import parse_max_grad_norm, parse_skip_nonfinite
+        from ..train_ops import parse_accum_steps, parse_max_grad_norm, parse_skip_nonfinite
+        self.accum_steps = parse_accum_steps(accum_steps)
+        self.stepped, self._loss_acc = False, None  # the last optimize_parameters() applied a step; the open group's loss record
         self.grad_clip_norm = parse_max_grad_norm(grad_clip_norm, "grad_clip_norm")
         self.skip_nonfinite_steps = parse_skip_nonfinite(skip_nonfinite_steps, "skip_nonfinite_steps")
         self.grad_info, self.skipped_steps = None, 0
@@ -161,7 +167,7 @@ class CLIPDriftModel():
             self.grad_sync.broadcast_parameters(list(self.drift_net.parameters()) + list(self.noise_net.parameters()))
         if if_train:
             from ..train_ops import FusedAdam
-            guard = dict(max_grad_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite_steps)
+            guard = dict(max_grad_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite_steps, accum_steps=self.accum_steps)
             self.drift_optimizer = FusedAdam(self.drift_net.parameters(), lr=drift_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2), **guard)
             self.noise_optimizer = FusedAdam(self.noise_net.parameters(), lr=noise_net_lr, weight_decay=weight_decay_drift, betas=(beta1, beta2), **guard)
             self.drift_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.drift_optimizer, T_max=nepoch, eta_min=eta_min)
@@ -212,7 +218,26 @@ class CLIPDriftModel():
         return message + '(skipped={:d})'.format(gi['skipped_steps'])
 
     def optimize_parameters(self):  # :231-232
+        """-> (loss, forward time); with accum_steps > 1 the loss is None unless this call closed its group (self.stepped), and then
+        the mean over the group"""
         return self.optimize_parameters_inputRes()
+
+    @property
+    def micro_step(self):
+        """micro-steps of the open group taken so far (0: no group is open)"""
+        return self.drift_optimizer.micro_step
+
+    def set_accum_steps(self, accum_steps):
+        """micro-steps per optimizer step of both optimizers, from the next group on; refused while a group is open"""
+        for o in (self.drift_optimizer, self.noise_optimizer):
+            o.set_accum_steps(accum_steps)
+        self.accum_steps = self.drift_optimizer.accum_steps
+
+    def discard_accumulated(self):
+        """drop an open group of micro-steps (gradients and loss records).  -> micro-steps dropped"""
+        dropped = max(o.discard_accumulated() for o in (self.drift_optimizer, self.noise_optimizer))
+        self._loss_acc = None
+        return dropped
 
     def optimize_score_map(self, score_maps, label, size=None, mult=[1, 2, 4, 8], want_grads=False):
         """sum_i MSE(score_maps[i], Resize((size[0]//mult[i], size[1]//mult[i]))(label)) / 2   (:234-240).
@@ -429,5 +454,7 @@ def create_CLIPDriftModel(train_opt, model_opt, phase='train', **extra):  # :758
         kw.update(grad_clip_norm=model_opt['grad_clip_norm'])
     if model_opt.get('skip_nonfinite_steps') is not None:
         kw.update(skip_nonfinite_steps=model_opt['skip_nonfinite_steps'])
+    if model_opt.get('accum_steps') is not None:
+        kw.update(accum_steps=model_opt['accum_steps'])
     kw.update(extra)
     return CLIPDriftModel(model_opt['text_encoder_pretrain_path'], **kw)

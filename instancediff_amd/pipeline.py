@@ -17,14 +17,15 @@ def load_options(path=DEFAULT_YAML, is_train=False):
 
 
 def build(opt=None, phase="test", device=None, T=None, seed=0, dist=False, sde_overrides=None, score_map_dropout=None, score_map_decoder=None, score_map_if_flash=None,
-          conv_dtype=None, grad_clip_norm=None, skip_nonfinite_steps=None):
+          conv_dtype=None, grad_clip_norm=None, skip_nonfinite_steps=None, accum_steps=None):
     """-> (model: CLIPDriftModel, sde).  Random-init weights (seed) as the reference does for a fresh run.
     score_map_dropout: overrides the model option of that name (training-mode dropout of the ScoreMapModule decoder blocks; 0.1).
     score_map_decoder: overrides the model option of that name ("ContextDecoder" | "ContextDecoder_Hierachical").
     score_map_if_flash: overrides the model option of that name (the fp16 form of the Hierachical decoder's attentions).
     conv_dtype: overrides the model option of that name ("f32" | "bf16": the operand precision of the 3x3 convs).
     grad_clip_norm / skip_nonfinite_steps: override the model options of those names (the training step's gradient guard: clip each net's
-    gradient to that global L2 norm; leave out a step whose gradient is not finite)."""
+    gradient to that global L2 norm; leave out a step whose gradient is not finite).
+    accum_steps: overrides the model option of that name (gradient accumulation: optimize_parameters() calls per optimizer step)."""
     opt = opt or load_options()
     train_opt = copy.deepcopy(dict(opt['train']))
     train_opt['dist'] = dist
@@ -48,6 +49,9 @@ def build(opt=None, phase="test", device=None, T=None, seed=0, dist=False, sde_o
     if skip_nonfinite_steps is not None:
         model_opt = copy.copy(model_opt)
         model_opt['skip_nonfinite_steps'] = skip_nonfinite_steps
+    if accum_steps is not None:
+        model_opt = copy.copy(model_opt)
+        model_opt['accum_steps'] = accum_steps
     torch.manual_seed(seed)
     from .models.drift_noise_model import create_CLIPDriftModel  # registry target, imported for the device kwarg
     model = create_CLIPDriftModel(train_opt, model_opt, phase=phase, device=device) if device is not None else \

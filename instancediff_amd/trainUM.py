@@ -1,14 +1,22 @@
 #!/usr/bin/env python3
 """Training driver with the reference's CLI and option surface (trainUM.py:81-359):
 
-    python -m instancediff_amd.trainUM -opt <yaml> [--launcher none|pytorch] [--local_rank N] [--grad-clip-norm C] [--skip-nonfinite-steps]
+    python -m instancediff_amd.trainUM -opt <yaml> [--launcher none|pytorch] [--local_rank N] [--grad-clip-norm C] [--skip-nonfinite-steps] [--accum-steps K]
     python -m torch.distributed.run --nproc-per-node N -m instancediff_amd.trainUM -opt <yaml> --launcher pytorch
 
 Differences from the reference (all in SURVEY.md §2.1/§3.1): world size comes from the environment (the
 reference hard-codes 2, :66); one flat RCCL gradient all-reduce per optimizer per step instead of 10 DDP wrappers;
 validation metrics (RMSE/PSNR/SSIM, :314-329) are computed on the device by one kernel; `max_iters` (optional
 key under `train:`) bounds a run for smoke tests; `--grad-clip-norm` / `--skip-nonfinite-steps` (model options grad_clip_norm /
-skip_nonfinite_steps) switch on the gradient guard, whose norms, coefficients and skip count are then appended to the printed line.
+skip_nonfinite_steps) switch on the gradient guard, whose norms, coefficients and skip count are then appended to the printed line;
+`--accum-steps K` (model option accum_steps) accumulates the gradients of K loader batches per optimizer step: `batch_size` stays
+what the loader yields per micro-step, while the iteration count -- print_freq, save_checkpoint_freq, val_freq, max_iters, the resume
+`iter` -- counts optimizer steps.  A group left open at the end of an epoch continues into the next one; one left open at the end of
+training is discarded.  Micro-batches are assumed to be of equal size (the step applies the mean over the group).
+Checkpoints are taken at group ends only.  An epoch checkpoint that falls due while a group is open is therefore written when that
+group closes, inside the next epoch, still as `epoch_<e>` with epoch e in its state: its weights then include the fewer than K
+micro-batches of epoch e + 1 that completed the group, and a resume from it, which restarts epoch e + 1 at its first batch, feeds
+those micro-batches a second time.
 """
 import argparse
 import math
@@ -63,16 +71,20 @@ def build_parser():
                         help="clip each net's gradient to this global L2 norm (overrides the model option grad_clip_norm)")
     parser.add_argument("--skip-nonfinite-steps", action="store_true",
                         help="leave out an optimizer step whose gradient is NaN or inf (overrides the model option skip_nonfinite_steps)")
+    parser.add_argument("--accum-steps", type=int, default=None, metavar="K",
+                        help="accumulate the gradients of K loader batches per optimizer step (overrides the model option accum_steps)")
     return parser
 
 
 def apply_model_overrides(opt, args):
-    """the command line's gradient-guard switches -> the options of the model that train.which_model names"""
+    """the command line's gradient-guard and accumulation switches -> the options of the model that train.which_model names"""
     model_opt = opt["models"][opt["train"]["which_model"]]
     if args.grad_clip_norm is not None:
         model_opt["grad_clip_norm"] = args.grad_clip_norm
     if args.skip_nonfinite_steps:
         model_opt["skip_nonfinite_steps"] = True
+    if args.accum_steps is not None:
+        model_opt["accum_steps"] = args.accum_steps
     return opt
 
 
@@ -125,17 +137,26 @@ def main(argv=None):
     model.set_sde(sde)
     max_iters = opt["train"]["max_iters"] or 0
 
-    print("Start training from epoch: {:d}, iter: {:d}".format(start_epoch, current_step))
+    accum = getattr(model, "accum_steps", 1)
+    print("Start training from epoch: {:d}, iter: {:d}; effective batch: {:d} (batch_size {:d} x accum_steps {:d} x world {:d})".format(
+        start_epoch, current_step, train_bs * accum * world, train_bs, accum, world))
     done = False
+    epoch_save = None  # an epoch checkpoint that fell due while a group of micro-steps was open: taken at that group's end
     for epoch in range(start_epoch, total_epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
         model.reinit_loss_message()
         for ii, td in enumerate(iterate_batches(train_set, train_bs, sampler=sampler, shuffle=True, seed=epoch)):
-            current_step += 1
             data = {'input': td["LQ"], 'target': td["GT"], 'names': td["name"], 'A_emb': td["A_emb"]}
             model.feed_data(data)
             loss, dur = model.optimize_parameters()
+            if not getattr(model, "stepped", True):  # a micro-step of an open group (accum_steps > 1): no optimizer step yet
+                continue
+            current_step += 1
+            if epoch_save is not None:  # (a resume from it sees this epoch's micro-batches of the group again: see the module text)
+                model.save(f"epoch_{epoch_save}", opt["path"]["models"])
+                model.save_training_state(epoch_save, current_step, opt["path"]["training_state"])
+                epoch_save = None
             message = "<epoch:{:3d}, iter:{:8,d}, lr:{:.3e}> (fwd time {:.4f}) ".format(epoch, current_step, model.get_current_learning_rate(), dur)
             message += model.get_loss_message()
             message += model.get_grad_message()  # empty unless grad_clip_norm / skip_nonfinite_steps is on
@@ -154,8 +175,14 @@ def main(argv=None):
         if done:
             break
         if epoch % 5 == 0 and rank <= 0:
-            model.save(f"epoch_{epoch}", opt["path"]["models"])
-            model.save_training_state(epoch, current_step, opt["path"]["training_state"])
+            if getattr(model, "micro_step", 0):  # checkpoints are taken at group ends: the open group continues into the next epoch
+                epoch_save = epoch
+            else:
+                model.save(f"epoch_{epoch}", opt["path"]["models"])
+                model.save_training_state(epoch, current_step, opt["path"]["training_state"])
+    dropped = model.discard_accumulated() if accum > 1 else 0
+    if dropped and rank <= 0:
+        print(f"Discarded an open group of {dropped} of {accum} accumulated micro-steps at the end of training.")
     if rank <= 0:
         model.save("latest", opt["path"]["models"])
         print("End of training.")

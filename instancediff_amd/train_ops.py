@@ -1229,6 +1229,13 @@ def parse_skip_nonfinite(value, name="skip_nonfinite"):
     return value
 
 
+def parse_accum_steps(value, name="accum_steps"):
+    """an int >= 1 and nothing else (no bools, floats or strings)"""
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"{name} must be an int >= 1, got {value!r}")
+    return value
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (L2 weight decay added to the gradient; config.yml:138-143) in ONE kernel launch per
     parameter group: parameters, gradients and both moments live in flat buffers (the parameters' .data / .grad are
@@ -1239,12 +1246,23 @@ class FusedAdam(torch.optim.Optimizer):
         grad_scale -- torch.nn.utils.clip_grad_norm_(params, max_grad_norm) in front of torch.optim.Adam.
     skip_nonfinite: a step whose gradient norm is NaN or inf leaves parameters and moments untouched, and does not count.
     Norm, coefficient and the applied flag stay on the device (last_info, 4 floats: idiff_grad_guard's record); step() reads nothing
-    back.  settle() tells the host-side step count about a skipped step."""
+    back.  settle() tells the host-side step count about a skipped step.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+    Gradient accumulation (accum_steps = k, default 1 = off, and step() is then today's step, launch for launch): every step() is a
+    micro-step.  The first of a group gathers its gradients into the flat buffers as always; the others ADD theirs
+    (idiff_gather_segments_acc: ((g0 + g1) + g2) ..., a parameter without a gradient keeps its sum), and only the k-th applies Adam --
+    plain or guarded -- to the MEAN of the k gradients (grad_scale / k inside the kernels and the guard's norm) and returns True; the
+    others launch nothing else, leave the step counts and WEIGHT_EPOCH alone and return False.  The mean assumes micro-batches of
+    equal size.  A NaN / inf in any micro-step makes the group's sum non-finite: with skip_nonfinite the group is skipped, once."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False,
+                 accum_steps=1):
         max_grad_norm, skip_nonfinite = parse_max_grad_norm(max_grad_norm), parse_skip_nonfinite(skip_nonfinite)
+        accum_steps = parse_accum_steps(accum_steps)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, skip_nonfinite
+        self.accum_steps = accum_steps
+        self._held = 0  # micro-gradients the flat buffers hold (0 .. accum_steps - 1 between two step() calls)
         self.last_info = self._part = None  # device buffers of the guard, allocated by the first guarded step
         self.skipped_steps = 0
         self._unsettled = False
@@ -1280,6 +1298,29 @@ class FusedAdam(torch.optim.Optimizer):
     def guarded(self):
         return self.max_grad_norm is not None or self.skip_nonfinite
 
+    def set_accum_steps(self, accum_steps):
+        """micro-steps per optimizer step from the next group on (see the class); refused while a group is open"""
+        accum_steps = parse_accum_steps(accum_steps)
+        if self._held:
+            raise RuntimeError(f"set_accum_steps: a group of micro-steps is open ({self._held} of {self.accum_steps} gradients held); "
+                               "finish it or discard_accumulated() first")
+        self.accum_steps = accum_steps
+
+    @property
+    def micro_step(self):
+        """gradients of the open group the flat buffers hold: 0 .. accum_steps - 1"""
+        return self._held
+
+    @property
+    def boundary_next(self):
+        """the next step() closes its group: it applies Adam"""
+        return self._held + 1 >= self.accum_steps
+
+    def discard_accumulated(self):
+        """drop an open group of micro-steps: the next gradient is gathered as a group's first.  -> micro-gradients dropped"""
+        dropped, self._held = self._held, 0
+        return dropped
+
     def flat_grads(self):
         """the flat gradient buffers, complete: gradients autograd left in tensors of their own are gathered first (one launch)"""
         self._collect()
@@ -1290,7 +1331,8 @@ class FusedAdam(torch.optim.Optimizer):
         backward produces (no `grad += g` launch per parameter, no zero-fill of the flat buffer); _collect() moves them into the flat
         buffer in ONE launch (a parameter that received no gradient gets zeros) and re-binds p.grad to its view of the flat buffer.
         set_to_none=False: torch.optim semantics -- the flat buffer is zero-filled and every p.grad is (re-)bound to its view of it, so
-        a backward ACCUMULATES into it."""
+        a backward ACCUMULATES into it.  While a group of micro-steps is open (accum_steps > 1) the flat buffer holds the group's sum
+        and is not zero-filled: the views are re-bound, and a backward accumulates onto the sum."""
         for f in self._flat:
             if f is None:
                 continue
@@ -1298,7 +1340,8 @@ class FusedAdam(torch.optim.Optimizer):
                 for p in f['params']:
                     p.grad = None
             else:
-                f['g'].zero_()
+                if not self._held:
+                    f['g'].zero_()
                 o = 0
                 for p in f['params']:
                     n = p.numel()
@@ -1307,7 +1350,11 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def _collect(self):
+        """Per-parameter gradient tensors -> the flat buffers, one launch per group.  Nothing held (always so with accum_steps = 1): they
+        are assigned, zeros where a parameter has no gradient.  With micro-gradients held they are ADDED, and a parameter without a
+        gradient keeps what it has.  Either way p.grad is the flat view afterwards, so a second call without a new backward does nothing."""
         import numpy as np
+        add = self._held > 0
         for f in self._flat:
             if f is None:
                 continue
@@ -1333,9 +1380,13 @@ class FusedAdam(torch.optim.Optimizer):
                 for p in f['params']:
                     n = p.numel()
                     if p.grad is None:
-                        f['g'][o:o + n].zero_()
+                        if not add:
+                            f['g'][o:o + n].zero_()
                     elif p.grad.data_ptr() != base + 4 * o:
-                        f['g'][o:o + n].copy_(p.grad.reshape(-1))
+                        if add:
+                            f['g'][o:o + n].add_(p.grad.reshape(-1))
+                        else:
+                            f['g'][o:o + n].copy_(p.grad.reshape(-1))
                     o += n
             else:
                 # The segment table goes up from a persistent PINNED staging buffer with a non-blocking copy: a pageable-memory copy
@@ -1356,7 +1407,11 @@ class FusedAdam(torch.optim.Optimizer):
                 dev_tab = st[1][:nrec]
                 dev_tab.copy_(st[0][:nrec], non_blocking=True)
                 st[2].record()
-                check(_lib.load().idiff_gather_segments(dev_tab.data_ptr(), nrec, int(nb.sum()), _p(f['g']), _stream()), "gather_segments")
+                lib = _lib.load()
+                if add:
+                    check(lib.idiff_gather_segments_acc(dev_tab.data_ptr(), nrec, int(nb.sum()), _p(f['g']), _stream()), "gather_segments_acc")
+                else:
+                    check(lib.idiff_gather_segments(dev_tab.data_ptr(), nrec, int(nb.sum()), _p(f['g']), _stream()), "gather_segments")
                 f['_keep'] = [p.grad for p in f['params']]  # the gathered tensors stay alive until the next collect: the launch is asynchronous
             o = 0
             for p in f['params']:
@@ -1366,25 +1421,36 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if self.guarded:
-            return self._guarded_step()
-        lib = _lib.load()
+        """One micro-step: collect this backward's gradients; the accum_steps-th of a group applies the plain or guarded Adam step to
+        the group's mean gradient.  -> True when Adam ran (every call with accum_steps = 1)."""
         self._collect()
+        self._held += 1
+        if self._held < self.accum_steps:
+            return False
+        self._held = 0
+        # (x / 1 == x: with accum_steps = 1 the kernels get grad_scale itself)
+        self._apply(self.grad_scale / self.accum_steps)
+        return True
+
+    def _apply(self, scale):
+        """the Adam launches of a group's end, on the flat gradient times `scale`"""
+        if self.guarded:
+            return self._guarded_step(scale)
+        lib = _lib.load()
         for group, f in zip(self.param_groups, self._flat):
             if f is None:
                 continue
             f['step'] += 1
             b1, b2 = group['betas']
             check(lib.idiff_adam_step(_p(f['p']), _p(f['g']), _p(f['m']), _p(f['v']), f['p'].numel(), group['lr'], b1, b2, group['eps'],
-                                      group['weight_decay'], self.grad_scale, f['step'], _stream()), "adam_step")
+                                      group['weight_decay'], scale, f['step'], _stream()), "adam_step")
         WEIGHT_EPOCH[0] += 1
 
-    def _guarded_step(self):
+    def _guarded_step(self, scale):
         """sum of squares per group -> one guard launch over all groups' partials -> one device-scaled Adam launch per group, back
         to back on the current stream.  f['step'] advances as in the plain step (the host-side bias corrections need it before the
         device knows whether the step applies); settle() takes it back for a skipped step."""
         lib = _lib.load()
-        self._collect()
         if self._unsettled:  # nobody settled the previous step: fetch its record ourselves (one small copy)
             self.settle()
         live = [(group, f) for group, f in zip(self.param_groups, self._flat) if f is not None]
@@ -1398,13 +1464,13 @@ class FusedAdam(torch.optim.Optimizer):
                 self.last_info = torch.zeros(4, device=dev, dtype=torch.float32)
         for k, (_, f) in enumerate(live):
             check(lib.idiff_grad_sumsq(_p(f['g']), f['g'].numel(), self._part.data_ptr() + 4 * k * parts, _stream()), "grad_sumsq")
-        check(lib.idiff_grad_guard(_p(self._part), len(live), self.grad_scale, self.max_grad_norm or 0.0, int(self.skip_nonfinite),
+        check(lib.idiff_grad_guard(_p(self._part), len(live), scale, self.max_grad_norm or 0.0, int(self.skip_nonfinite),
                                    _p(self.last_info), _stream()), "grad_guard")
         for group, f in live:
             f['step'] += 1
             b1, b2 = group['betas']
             check(lib.idiff_adam_step_dev(_p(f['p']), _p(f['g']), _p(f['m']), _p(f['v']), f['p'].numel(), group['lr'], b1, b2, group['eps'],
-                                          group['weight_decay'], self.grad_scale, f['step'], _p(self.last_info), _stream()), "adam_step_dev")
+                                          group['weight_decay'], scale, f['step'], _p(self.last_info), _stream()), "adam_step_dev")
         self._unsettled = True
         WEIGHT_EPOCH[0] += 1
 
@@ -1427,6 +1493,9 @@ class FusedAdam(torch.optim.Optimizer):
         return True
 
     def state_dict(self):
+        if self._held:
+            raise RuntimeError(f"state_dict: a group of micro-steps is open ({self._held} of {self.accum_steps} gradients held); checkpoints "
+                               "are taken at group ends (or discard_accumulated() first)")
         if self._unsettled:
             self.settle()
         sd = super().state_dict()
@@ -1503,7 +1572,8 @@ def forward_backward_inputRes(model):
     Losses and their gradients come from the HIP loss kernel; autograd is entered with explicit output gradients.  Leaves the
     parameter gradients in the optimizers' flat buffers -- with the data-parallel exchange of each buffer already STARTED when
     the model has a grad_sync (finish() it before reading them); returns (loss record [10] on the device, forward time, use_dsm,
-    use_nsm)."""
+    use_nsm).  With gradient accumulation (the optimizers' accum_steps > 1) the gradients are added to those the flat buffers hold,
+    and the exchange is started only by the group's last micro-step: one all-reduce per optimizer per OPTIMIZER step."""
     import time
     st = time.time()
     m = model
@@ -1515,7 +1585,8 @@ def forward_backward_inputRes(model):
     rec = torch.zeros(10, device=m.device, dtype=torch.float32)  # dl, nl, dsm x4, nsm x4
     m.noise_optimizer.zero_grad()
     m.drift_optimizer.zero_grad()
-    sync = m.grad_sync
+    # the exchange travels once per optimizer step: on the sum the group's last micro-step completes
+    sync = m.grad_sync if m.drift_optimizer.boundary_next else None
 
     def fwd(net, xb, target, slot_main, slot_sm, use_sm):
         with torch.enable_grad():
@@ -1579,13 +1650,30 @@ def train_step_inputRes(model):
     """One optimisation step (drift_noise_model.py:242-312): forward_backward_inputRes, the data-parallel gradient exchange,
     two Adam steps, loss bookkeeping with ONE device->host copy.  With a gradient guard on (FusedAdam: max_grad_norm / skip_nonfinite) the
     same copy brings both optimizers' {norm, coef, applied} records: model.grad_info = {'drift' / 'noise': {'norm', 'coef', 'skipped'},
-    'skipped_steps': iterations so far in which a step was skipped}.  The EMAs update after a skipped step too (harmless)."""
+    'skipped_steps': iterations so far in which a step was skipped}.  The EMAs update after a skipped step too (harmless).
+
+    With gradient accumulation (model.accum_steps = k > 1) a call is a micro-step: forward, backward, the gradients added into the flat
+    buffers, the loss record added to the group's on the device (one launch) -- and nothing else unless it is the group's k-th: no
+    exchange, no Adam, no EMA update, no device->host copy, no synchronisation; model.stepped is False and the loss returned is None.
+    The k-th does all of the above on the mean gradient, copies the group's summed loss record once, and loss_info / grad_info /
+    skipped_steps advance once, with the group means; model.stepped is True."""
     m = model
+    k = m.drift_optimizer.accum_steps
+    last = m.drift_optimizer.boundary_next
     rec, iter_time, use_dsm, use_nsm = forward_backward_inputRes(m)
-    scale = m.grad_sync.finish() if m.grad_sync is not None else 1.0  # the exchanges were started during the backward
+    if k > 1:
+        if m._loss_acc is not None:
+            rec = ops.axpby(m._loss_acc, rec, 1.0, 1.0, out=m._loss_acc)
+        m._loss_acc = None if last else rec
+    if m.grad_sync is not None and last:
+        scale = m.grad_sync.finish()  # the exchanges were started during the backward
+    else:
+        scale = 1.0
     m.noise_optimizer.grad_scale = m.drift_optimizer.grad_scale = scale
     m.noise_optimizer.step()
-    m.drift_optimizer.step()
+    m.stepped = m.drift_optimizer.step()  # both optimizers count the same micro-steps
+    if not m.stepped:
+        return None, iter_time
     for ema in (getattr(m, "dp_ema", None), getattr(m, "np_ema", None), m.dn_ema, m.nn_ema):
         if ema is not None:  # the reference builds the EMA objects but never calls update() (SURVEY.md §5)
             ema.update()
@@ -1601,13 +1689,15 @@ def train_step_inputRes(model):
         m.skipped_steps += any(g is not None and g['skipped'] for g in (gi['drift'], gi['noise']))
         gi['skipped_steps'] = m.skipped_steps
         m.grad_info = gi
+    if k > 1:
+        r[:10] /= k  # the group's sums -> means
     dl, nl = float(r[0]), float(r[1])
     dsml = float(r[2:6].sum()) / 2.0 if use_dsm else 0.0
     nsml = float(r[6:10].sum()) / 2.0 if use_nsm else 0.0
     loss = dl + nl + dsml + nsml
     li = m.loss_info
     li['latest'].update(l=loss, nsml=nsml, dsml=dsml, nl=nl, dl=dl)
-    for k, v in (('l', loss), ('dl', dl), ('nl', nl), ('dsml', dsml), ('nsml', nsml)):
-        li['avg'][k] += v
+    for key, v in (('l', loss), ('dl', dl), ('nl', nl), ('dsml', dsml), ('nsml', nsml)):
+        li['avg'][key] += v
     li['num'] += 1
     return loss, iter_time
