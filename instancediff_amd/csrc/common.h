@@ -49,6 +49,21 @@ inline hipError_t idiff_ensure_dyn_lds(idiff_dyn_lds_cache& c, const void* fn, s
     return hipSuccess;
 }
 
+// Compute units of the current device (the persistent kernels' grid), cached per device like the attribute above.  False: the query failed.
+inline bool idiff_num_cu(int* n) {
+    static std::atomic<int> count[64];  // 0 = not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    const bool cached = dev >= 0 && dev < 64;
+    int v = cached ? count[dev].load(std::memory_order_relaxed) : 0;
+    if (v <= 0) {
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return false;
+        if (cached) count[dev].store(v, std::memory_order_relaxed);
+    }
+    *n = v;
+    return true;
+}
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 

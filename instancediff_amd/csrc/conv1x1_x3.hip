@@ -17,11 +17,8 @@
 //   are copied verbatim.  LDS: B planes 51 KB + A planes 12 KB, single buffer (the next two chunks travel in 76 registers) -> two
 //   workgroups per CU, one splitting while the other multiplies.  Epilogue = conv_igemm.hip's flattened form (accumulators through
 //   LDS as [32 co][256 px] halves, 16-byte row segments; bias, per-(b,c) vector, residual, "+ silu(a*aux+b)"); no GroupNorm partials.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_args.h"
+#include "wino_common.h"
 
 using idiff_detail::ConvArgs;
 
@@ -62,13 +59,7 @@ __device__ __forceinline__ void split3(const float (&x)[8], uintx4& p1, uintx4& 
     p3 = uintx4{pack_hi(u3[1], u3[0]), pack_hi(u3[3], u3[2]), pack_hi(u3[5], u3[4]), pack_hi(u3[7], u3[6])};
 }
 
-// a wave-uniform pointer pinned to scalar registers (a resource base left in VGPRs costs a waterfall loop per buffer load)
-template <typename T>
-__device__ __forceinline__ T* scalar_ptr(const T* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
+using idiff_wino::scalar_ptr;  // a wave-uniform pointer pinned to scalar registers
 
 __device__ __forceinline__ floatx4 mma(const uintx4& a, const uintx4& b, const floatx4& c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);

@@ -25,15 +25,14 @@
 //   Same fused gather (virtual concat, nearest x2 upsample, GroupNorm/FiLM affine + SiLU prologue) and the same
 //   epilogue contract (bias, residual, per-(b,c) vector, "+silu(a*aux+b)", GroupNorm partials per 8x32 patch) as
 //   conv_igemm.hip; the two kernels are interchangeable behind idiff_conv2d_fwd.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_args.h"
+#include "wino_common.h"
 
 using idiff_detail::ConvArgs;
 
 namespace {
+
+using namespace idiff_wino;
 
 constexpr int CK = 8;
 constexpr int TW = 32, TH = 8;
@@ -49,37 +48,6 @@ constexpr int NL = R_FLOATS / NT;              // 6 gathered elements per thread
 constexpr int NU = U_FLOATS / 4 / NT;          // 4 float4 of weights per thread per chunk
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
-
-// sum over each 16-lane row by DPP prefix adds (row_shr 1, 2, 4, 8; zeros shift in): lane 15 of the row ends with the total
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp_row_shr<0x111>(v);
-    v += dpp_row_shr<0x112>(v);
-    v += dpp_row_shr<0x114>(v);
-    v += dpp_row_shr<0x118>(v);
-    return v;
-}
-
-// -DIDIFF_WINO_TRACE: per-phase cycle counts (s_memtime) summed over all items, printed by the launcher (debug builds)
-#ifdef IDIFF_WINO_TRACE
-#define TRACE_PARAM , long long* trace
-#define TRACE_INIT long long tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tr_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-#define TRACE_MARK(k)                                      \
-    tr_t[k] = __builtin_readcyclecounter();                \
-    if (k > 0) tr_acc[k - 1] += tr_t[k] - tr_t[k - 1];
-#define TRACE_FINI                                                                  \
-    if (tid == 0) {                                                                 \
-        for (int q_ = 0; q_ < 7; ++q_) atomicAdd((unsigned long long*)trace + q_, (unsigned long long)tr_acc[q_]); \
-    }
-#else
-#define TRACE_PARAM
-#define TRACE_INIT
-#define TRACE_MARK(k)
-#define TRACE_FINI
-#endif
 
 #ifndef IDIFF_WINO_PD
 #define IDIFF_WINO_PD 1  // operand prefetch distance of the MFMA loop, in Winograd positions
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(NT) void conv_wino_kernel(const ConvArgs a TRACE_PA
     fetch_consts();
     if (SPEC == 2 && tid < 2 * a.C0r) protab[tid] = pre_p;  // parity 0; visible after the first item's top barrier
     int parity = 0;
-    TRACE_INIT
+    TRACE_INIT(7)
 
     for (int item = first; item < last; item += G) {
         const int b = it_b, tile = it_tile, co0 = it_co0, y0 = it_y0, x0 = it_x0;  // the epilogue's view of this item
@@ -493,7 +461,7 @@ __global__ __launch_bounds__(NT) void conv_wino_kernel(const ConvArgs a TRACE_PA
         }
         TRACE_MARK(7)
     }
-    TRACE_FINI
+    TRACE_FINI(7)
 }
 
 template <int MODE, int SPEC, bool RAG>
@@ -506,16 +474,11 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
         hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
         if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd): hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd): cannot query the CU count");
-        num_cu = n;
-    }
+    int num_cu = 0;
+    if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd): cannot query the CU count");
     const int total = (int)a.total_wg;
-    const int per = (total + num_cu - 1) / num_cu;          // items per workgroup
-    const int grid = (total + per - 1) / per;               // <= one workgroup per CU, none empty, strided item order
+    int per = 0;                                                  // items per workgroup
+    const int grid = persistent_grid(total, num_cu, &per);        // <= one workgroup per CU, none empty, strided item order
 #ifdef IDIFF_WINO_TRACE
     static long long* tr = nullptr;
     if (!tr) (void)hipMalloc(&tr, 8 * sizeof(long long));
@@ -533,12 +496,6 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
     return IDIFF_OK;
 }
 
-template <int MODE, int SPEC>
-int launch(const ConvArgs& a, hipStream_t st) {
-    if (a.Hout % TH || a.Wout % TW) return launch_rag<MODE, SPEC, true>(a, st);
-    return launch_rag<MODE, SPEC, false>(a, st);
-}
-
 // U = G g G^T for one (co, ci); G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int transpose) {
     // conv seen by the kernel: Co x Ci (swapped when transpose)
@@ -548,11 +505,7 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int co = i % Co, ci = i / Co;
         float g[3][3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                g[p][q] = transpose ? w[((long long)ci * Cin + co) * 9 + (2 - p) * 3 + (2 - q)] : w[((long long)co * Cin + ci) * 9 + p * 3 + q];
+        load_taps(w, Cin, co, ci, transpose, g);
         float t[4][3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -577,7 +530,11 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     }
 }
 
-bool wino_disabled() {
+}  // namespace
+
+namespace idiff_detail {
+
+bool winograd_disabled() {
     static const bool off = [] {
         const char* e = getenv("IDIFF_WINOGRAD");
         return e && e[0] == '0';
@@ -585,12 +542,8 @@ bool wino_disabled() {
     return off;
 }
 
-}  // namespace
-
-namespace idiff_detail {
-
 bool conv_wino_eligible(const ConvArgs& a, int ks, int mode) {
-    if (ks != 3 || !a.wwino || wino_disabled()) return false;
+    if (ks != 3 || !a.wwino || winograd_disabled()) return false;
     if (mode != IDIFF_CONV_NORMAL && mode != IDIFF_CONV_UPSAMPLE2) return false;
     // any even image size from 24 columns up (there the GroupNorm-partial tiling of idiff_conv2d_num_tiles is the 8x32 patch for
     // both kernels); partial patches at the right / bottom border are masked
@@ -607,25 +560,13 @@ bool conv_wino_eligible(const ConvArgs& a, int ks, int mode) {
 }
 
 int launch_conv_wino(const ConvArgs& a, int mode, hipStream_t st) {
-    if (mode == IDIFF_CONV_UPSAMPLE2) return launch<IDIFF_CONV_UPSAMPLE2, 1>(a, st);
-    if (a.pro_a) return launch<IDIFF_CONV_NORMAL, 2>(a, st);
-    if (a.src1) return launch<IDIFF_CONV_NORMAL, 3>(a, st);
-    return launch<IDIFF_CONV_NORMAL, 1>(a, st);
+    return launch_spec_ladder(mode, a.pro_a != nullptr, a.src1 != nullptr, a.Hout % TH || a.Wout % TW, [&](auto mode_tag, auto spec_tag, auto rag_tag) {
+        return launch_rag<decltype(mode_tag)::value, decltype(spec_tag)::value, decltype(rag_tag)::value>(a, st);
+    });
 }
 
 }  // namespace idiff_detail
 
 extern "C" int idiff_pack_conv_weight_wino(const float* w, float* wwino, int Cout, int Cin, int transpose, idiff_stream_t stream) {
-    IDIFF_CHECK_ARG(w && wwino && Cout > 0 && Cin > 0, "pack_conv_weight_wino: bad args");
-    const int Co = transpose ? Cin : Cout, Ci = transpose ? Cout : Cin;
-    IDIFF_CHECK_ARG(Co % 16 == 0 && Ci % 8 == 0, "pack_conv_weight_wino: needs conv Cout %% 16 == 0 and Cin %% 8 == 0 (got %d, %d)", Co, Ci);
-    if (Co % 64) {  // partial last 64-channel block: its unused rows must read as zero
-        hipError_t e = hipMemsetAsync(wwino, 0, (size_t)16 * Ci * ((Co + 63) / 64) * 64 * sizeof(float), (hipStream_t)stream);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "pack_conv_weight_wino: hipMemsetAsync: %s", hipGetErrorString(e));
-    }
-    const long long n = (long long)Cout * Cin;
-    const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    hipLaunchKernelGGL(pack_wino_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, wwino, Cout, Cin, transpose);
-    IDIFF_CHECK_LAUNCH("pack_conv_weight_wino");
-    return IDIFF_OK;
+    return pack_entry<16>("pack_conv_weight_wino", pack_wino_kernel, w, wwino, Cout, Cin, transpose, stream);
 }

@@ -22,15 +22,14 @@
 //   Same fused gather (virtual concat, nearest x2 upsample, GroupNorm/FiLM affine + SiLU prologue) and the same epilogue
 //   contract (bias, residual, per-(b,c) vector, "+silu(a*aux+b)", GroupNorm partials per 8x32 patch) as conv_igemm.hip
 //   and conv_wino.hip; the three kernels are interchangeable behind idiff_conv2d_fwd.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_args.h"
+#include "wino_common.h"
 
 using idiff_detail::ConvArgs;
 
 namespace {
+
+using namespace idiff_wino;
 
 constexpr int CK = 4;
 constexpr int TW = 32, TH = 16;
@@ -47,50 +46,12 @@ constexpr int U_FLOATS = 9 * 4 * 64 * 4;   // 9216
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
-// Numbering of the 36 Winograd positions (u, v) into 9 quads of 4: the first four columns of row u fill quad PF(u), its last
-// two a half of quad PH(u) shared with the neighbouring row -- every row is one 16-byte and one 8-byte piece at fixed places,
-// so the transform writes them without looking at the row's parity.
-__host__ __device__ constexpr int PF(int u) { return (3 * u + 1) / 2; }       // 0, 2, 3, 5, 6, 8
-__host__ __device__ constexpr int PH(int u) { return 1 + 3 * (u / 2); }       // 1, 1, 4, 4, 7, 7
-__host__ __device__ constexpr int pos(int u, int v) { return v < 4 ? 4 * PF(u) + v : 4 * PH(u) + 2 * (u & 1) + (v - 4); }
-
 struct Geo4 {
     int np;        // 16x32 patches per sample
     int total;     // items = B * np * ncob
     int tiles_y8;  // rows of the 8x32 GroupNorm-partials grid
 };
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// sum over each 16-lane row by DPP prefix adds: lane 15 of the row ends with the total
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp_row_shr<0x111>(v);
-    v += dpp_row_shr<0x112>(v);
-    v += dpp_row_shr<0x114>(v);
-    v += dpp_row_shr<0x118>(v);
-    return v;
-}
-
-// -DIDIFF_WINO_TRACE: per-phase cycle counts (s_memtime) summed over all items, printed by the launcher (debug builds)
-#ifdef IDIFF_WINO_TRACE
-#define TRACE_PARAM , long long* trace
-#define TRACE_INIT long long tr_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define TRACE_MARK(k)                                                  \
-    tr_t[k] = __builtin_readcyclecounter();                            \
-    if (k > 0) tr_acc[k - 1] += tr_t[k] - tr_t[k - 1];                 \
-    else if (tr_t[3] != 0) tr_acc[3] += tr_t[0] - tr_t[3];
-#define TRACE_FINI                                                                                                      \
-    if (tid == 0) {                                                                                                     \
-        for (int q_ = 0; q_ < 8; ++q_) atomicAdd((unsigned long long*)trace + q_, (unsigned long long)tr_acc[q_]);      \
-    }
-#else
-#define TRACE_PARAM
-#define TRACE_INIT
-#define TRACE_MARK(k)
-#define TRACE_FINI
-#endif
 #ifdef IDIFF_WINO_SLOTS  // with IDIFF_WINO_TRACE: per wave, cycles per chunk of the main loop spent working / waiting at the barrier
 #define SLOT_INIT long long sl_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, sl_t = 0;
 #define SLOT_START sl_t = __builtin_readcyclecounter();
@@ -113,35 +74,6 @@ __device__ __forceinline__ float row_sum16(float v) {
 #define SLOT_MARK(k)
 #define SLOT_FINI
 #endif
-
-// A wave-uniform pointer pinned to scalar registers.  Under register pressure the compiler may keep a uniform 64-bit address in
-// vector registers; a buffer resource built from it then costs a waterfall loop (readfirstlane + compare + exec masking) around
-// EVERY buffer load that uses it.
-__device__ __forceinline__ const float* scalar_ptr(const float* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-}
-
-// one 6-point input transform B^T x
-__device__ __forceinline__ void bt6(const float (&x)[6], float (&o)[6]) {
-    o[0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
-    const float p = __builtin_fmaf(-4.f, x[2], x[4]), q = __builtin_fmaf(-4.f, x[1], x[3]);
-    o[1] = p + q;
-    o[2] = p - q;
-    const float c = x[4] - x[2], e = x[3] - x[1];
-    o[3] = __builtin_fmaf(2.f, e, c);
-    o[4] = __builtin_fmaf(-2.f, e, c);
-    o[5] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]));
-}
-// one 6 -> 4 output transform A^T x
-__device__ __forceinline__ void at6(const float x0, const float x1, const float x2, const float x3, const float x4, const float x5, float (&o)[4]) {
-    const float s1 = x1 + x2, d1 = x1 - x2, s2 = x3 + x4, d2 = x3 - x4;
-    o[0] = (x0 + s1) + s2;
-    o[1] = __builtin_fmaf(2.f, d2, d1);
-    o[2] = __builtin_fmaf(4.f, s2, s1);
-    o[3] = __builtin_fmaf(8.f, d2, d1) + x5;
-}
 
 // SPEC: 1 = single source, no prologue; 2 = single source + GN/FiLM/SiLU prologue; 3 = two sources (virtual concat)
 // RAG: the image is not a multiple of the 16x32 patch (partial patches at the right / bottom border are masked)
@@ -233,26 +165,11 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
         p1B = scalar_ptr(SPEC == 3 ? a.src1 + (long long)it_b * a.bs1 : a.src0);
         nrB = 0x7fffffff;
     };
-    // Thread requests R[tid + i*512]: the R index itself enumerates (ci, row, col).  An element's load offset (bytes inside the
-    // sample) is -1 for pad slots and for elements outside the image: the range check fails and the DMA writes 0.0.  The six
-    // offsets of an item are decoded once and parked in LDS (thread-private entries); returns the item's padding mask.
+    // The six gather offsets of an item (gather_decode: element tid + i*512 of R) are decoded once and parked in LDS
+    // (thread-private entries); returns the item's padding mask.
     auto write_table = [&](const View& v) {
-        int t = tid;
-        asm volatile("" : "+v"(t));  // opaque: keeps the decode here, once per item, instead of hoisted and held in registers
-        unsigned om = 0;
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = t + i * NT;
-            const int ci = e / PSP;
-            const int rem = e - ci * PSP;
-            const int r = rem / RS;
-            const int c = rem - r * RS;
-            const int oy = v.y0 - 1 + r, ox = v.x0 - 1 + c;  // output-grid coordinates of the element
-            const bool in = rem < PS && c < RCOLS && (unsigned)oy < (unsigned)a.Hout && (unsigned)ox < (unsigned)a.Wout;
-            const int sp = MODE == IDIFF_CONV_UPSAMPLE2 ? (oy >> 1) * a.Win + (ox >> 1) : oy * a.Win + ox;
-            gtab[i * NT + tid] = in ? (ci * HWin + sp) * 4 : -1;
-            om |= (in ? 0u : 1u) << i;
-        }
+        unsigned om;
+        gather_decode<MODE, NT, NL, PSP, PS, RS, RCOLS>(tid, om, v.y0, v.x0, a, gtab, HWin);
         return om;
     };
     auto shift_B_to_A = [&]() { p0A = p0B, p1A = p1B, puA = puB, vA = vB, omaskA = omaskB; };
@@ -455,7 +372,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
         }
         return e;
     };
-    TRACE_INIT
+    TRACE_INIT(8)
     SLOT_INIT
 
     // ---- the workgroup's first item: the only pipeline fill of the launch --------------------------------------------------------
@@ -514,6 +431,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     bool young = false;  // the requests in flight were issued BEFORE an epilogue: its >= 16 stores are younger than they are
     for (int item = first; item < last; item += G) {
         TRACE_MARK(0)
+        TRACE_LAP(3)  // "to next item"
         floatx4 acc[36];  // started from C = 0 by the first chunk's MFMAs (no 144 v_mov per item)
         {
             // ONE barrier per chunk.  Chunk c runs its 9 position quads and, one slice per quad:
@@ -753,7 +671,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
         epar ^= 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the null item's requests (answered with zeros) still target this workgroup's LDS
-    TRACE_FINI
+    TRACE_FINI(8)
     SLOT_FINI
 }
 
@@ -779,13 +697,8 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
         hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
         if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4): hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4): cannot query the CU count");
-        num_cu = n;
-    }
+    int num_cu = 0;
+    if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4): cannot query the CU count");
     Geo4 g;
     const int tiles_y16 = (a.Hout + TH - 1) / TH;
     g.np = a.tiles_x * tiles_y16;
@@ -793,8 +706,8 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
     const long long total = (long long)a.B * g.np * a.ncob;
     if (total >= (1ll << 31)) IDIFF_FAIL(IDIFF_E_BADARG, "conv2d(winograd4): grid too large");
     g.total = (int)total;
-    const int per = (g.total + num_cu - 1) / num_cu;
-    const int grid = (g.total + per - 1) / per;
+    int per = 0;
+    const int grid = persistent_grid(g.total, num_cu, &per);
 #ifdef IDIFF_WINO_TRACE
     static long long* tr = nullptr;
     if (!tr) (void)hipMalloc(&tr, 32 * sizeof(long long));
@@ -820,13 +733,7 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
     return IDIFF_OK;
 }
 
-template <int MODE, int SPEC>
-int launch(const ConvArgs& a, hipStream_t st) {
-    if (a.Hout % TH || a.Wout % TW) return launch_rag<MODE, SPEC, true>(a, st);
-    return launch_rag<MODE, SPEC, false>(a, st);
-}
-
-// U = G g G^T for one (co, ci); G rows: [1/4,0,0], [-1/6,-1/6,-1/6], [-1/6,1/6,-1/6], [1/24,1/12,1/6], [1/24,-1/12,1/6], [0,0,1]
+// U = G g G^T for one (co, ci) (g6 of wino_common.h), stored by pos()
 __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int transpose) {
     const int Co = transpose ? Cin : Cout, Ci = transpose ? Cout : Cin;  // the conv seen by the kernel
     const int ncob = (Co + 63) / 64;
@@ -834,21 +741,7 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int co = i % Co, ci = i / Co;
         float gk[3][3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                gk[p][q] = transpose ? w[((long long)ci * Cin + co) * 9 + (2 - p) * 3 + (2 - q)] : w[((long long)co * Cin + ci) * 9 + p * 3 + q];
-        auto g6 = [](float x0, float x1, float x2, float(&o)[6]) {
-            o[0] = 0.25f * x0;
-            const float s = x0 + x2;
-            o[1] = (-1.f / 6.f) * (s + x1);
-            o[2] = (-1.f / 6.f) * (s - x1);
-            const float t = __builtin_fmaf(4.f, x2, x0);  // x0 + 4 x2
-            o[3] = (1.f / 24.f) * __builtin_fmaf(2.f, x1, t);
-            o[4] = (1.f / 24.f) * __builtin_fmaf(-2.f, x1, t);
-            o[5] = x2;
-        };
+        load_taps(w, Cin, co, ci, transpose, gk);
         float t[6][3];  // G g
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -909,26 +802,14 @@ int launch_conv_wino4(const ConvArgs& a, int mode, hipStream_t st) {
 #ifdef W4_ONLY  // register-pressure experiments: one instantiation
     return launch_rag<IDIFF_CONV_NORMAL, 1, false>(a, st);
 #else
-    if (mode == IDIFF_CONV_UPSAMPLE2) return launch<IDIFF_CONV_UPSAMPLE2, 1>(a, st);
-    if (a.pro_a) return launch<IDIFF_CONV_NORMAL, 2>(a, st);
-    if (a.src1) return launch<IDIFF_CONV_NORMAL, 3>(a, st);
-    return launch<IDIFF_CONV_NORMAL, 1>(a, st);
+    return launch_spec_ladder(mode, a.pro_a != nullptr, a.src1 != nullptr, a.Hout % TH || a.Wout % TW, [&](auto mode_tag, auto spec_tag, auto rag_tag) {
+        return launch_rag<decltype(mode_tag)::value, decltype(spec_tag)::value, decltype(rag_tag)::value>(a, st);
+    });
 #endif
 }
 
 }  // namespace idiff_detail
 
 extern "C" int idiff_pack_conv_weight_wino4(const float* w, float* wwino4, int Cout, int Cin, int transpose, idiff_stream_t stream) {
-    IDIFF_CHECK_ARG(w && wwino4 && Cout > 0 && Cin > 0, "pack_conv_weight_wino4: bad args");
-    const int Co = transpose ? Cin : Cout, Ci = transpose ? Cout : Cin;
-    IDIFF_CHECK_ARG(Co % 16 == 0 && Ci % 8 == 0, "pack_conv_weight_wino4: needs conv Cout %% 16 == 0 and Cin %% 8 == 0 (got %d, %d)", Co, Ci);
-    if (Co % 64) {  // partial last 64-channel block: its unused rows must read as zero
-        hipError_t e = hipMemsetAsync(wwino4, 0, (size_t)36 * Ci * ((Co + 63) / 64) * 64 * sizeof(float), (hipStream_t)stream);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "pack_conv_weight_wino4: hipMemsetAsync: %s", hipGetErrorString(e));
-    }
-    const long long n = (long long)Cout * Cin;
-    const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    hipLaunchKernelGGL(pack_wino4_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, wwino4, Cout, Cin, transpose);
-    IDIFF_CHECK_LAUNCH("pack_conv_weight_wino4");
-    return IDIFF_OK;
+    return pack_entry<36>("pack_conv_weight_wino4", pack_wino4_kernel, w, wwino4, Cout, Cin, transpose, stream);
 }

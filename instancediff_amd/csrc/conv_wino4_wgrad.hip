@@ -18,15 +18,14 @@
 //   Two barriers per chunk: [quads 0-4 | stage R of chunk c+1]  barrier  [quads 5-8 | transforms of chunk c+1, loads of chunk c+2]
 //   barrier.  The input gather has the forward kernel's semantics (virtual concat, GroupNorm/FiLM affine + SiLU prologue, zero
 //   padding after the activation), so the fused forward needs no materialised activated tensor for its backward.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_wgrad_args.h"
+#include "wino_common.h"
 
 using idiff_detail::WwArgs;
 
 namespace {
+
+using namespace idiff_wino;
 
 constexpr int NT = 512;
 constexpr int PR = 6, PC = 20, PS = PR * PC;  // patch rows, row stride (18 columns used: 16-byte aligned rows), floats per channel
@@ -37,40 +36,6 @@ constexpr int D_FLOATS = 9 * 2 * 64 * 4;      // 4608
 constexpr int E_FLOATS = 9 * 4 * 64 * 4;      // 9216
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
-
-// position numbering of conv_wino4.hip: row u = one 16-byte piece in quad PF(u) + one 8-byte piece in half of quad PH(u)
-__host__ __device__ constexpr int PF(int u) { return (3 * u + 1) / 2; }
-__host__ __device__ constexpr int PH(int u) { return 1 + 3 * (u / 2); }
-__host__ __device__ constexpr int pos(int u, int v) { return v < 4 ? 4 * PF(u) + v : 4 * PH(u) + 2 * (u & 1) + (v - 4); }
-
-__device__ __forceinline__ void bt6(const float (&x)[6], float (&o)[6]) {  // one 6-point input transform B^T x
-    o[0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
-    const float p = __builtin_fmaf(-4.f, x[2], x[4]), q = __builtin_fmaf(-4.f, x[1], x[3]);
-    o[1] = p + q;
-    o[2] = p - q;
-    const float c = x[4] - x[2], e = x[3] - x[1];
-    o[3] = __builtin_fmaf(2.f, e, c);
-    o[4] = __builtin_fmaf(-2.f, e, c);
-    o[5] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]));
-}
-// A x for a 4-point x: the six rows of A = [1 0 0 0; 1 1 1 1; 1 -1 1 -1; 1 2 4 8; 1 -2 4 -8; 0 0 0 1]
-__device__ __forceinline__ void a6(float x0, float x1, float x2, float x3, float (&o)[6]) {
-    const float s = x0 + x2, t = x1 + x3;
-    o[0] = x0;
-    o[1] = s + t;
-    o[2] = s - t;
-    const float p = __builtin_fmaf(4.f, x2, x0), q = __builtin_fmaf(8.f, x3, 2.f * x1);
-    o[3] = p + q;
-    o[4] = p - q;
-    o[5] = x3;
-}
-// sum_u G[u][p] m[u] for the six rows of G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
-__device__ __forceinline__ void gt3(float m0, float m1, float m2, float m3, float m4, float m5, float (&o)[3]) {
-    const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-    o[0] = __builtin_fmaf(0.25f, m0, __builtin_fmaf(-1.f / 6.f, s12, (1.f / 24.f) * s34));
-    o[1] = __builtin_fmaf(-1.f / 6.f, d12, (1.f / 12.f) * d34);
-    o[2] = __builtin_fmaf(-1.f / 6.f, s12, __builtin_fmaf(1.f / 6.f, s34, m5));
-}
 
 template <bool PRO>
 __global__ __launch_bounds__(NT) void wino4_wgrad_kernel(const WwArgs a) {
@@ -378,8 +343,7 @@ int launch(const WwArgs& a, hipStream_t st) {
 bool wino4_wgrad_disabled() {  // IDIFF_WGRAD4=0: weight gradients stay on the F(2x2,3x3) kernel (A/B runs)
     static const bool off = [] {
         const char* e = getenv("IDIFF_WGRAD4");
-        const char* w = getenv("IDIFF_WINOGRAD");
-        return (e && e[0] == '0') || (w && w[0] == '0');
+        return (e && e[0] == '0') || idiff_detail::winograd_disabled();
     }();
     return off;
 }

@@ -24,15 +24,14 @@
 //   In the in-order vmcnt queue the six raw patch loads of a chunk (HBM) are issued between two A loads, so an A quad is never
 //   waited for behind a raw load younger than six quad slots; the first window of an item is requested after its predecessor's
 //   epilogue (it would otherwise sit in 24 registers across it) and the workgroup's partner covers the drain of those stores.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_args.h"
+#include "wino_common.h"
 
 using idiff_detail::ConvArgs;
 
 namespace {
+
+using namespace idiff_wino;
 
 constexpr int CK = 4;
 constexpr int TW = 32, TH = 8;
@@ -51,53 +50,10 @@ constexpr int AW = 6;                      // A-operand window, in position quad
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
-// position numbering of idiff_pack_conv_weight_wino4 (conv_wino4.hip): row u = one 16-byte piece in quad PF(u) + one 8-byte piece
-// in half of quad PH(u)
-__host__ __device__ constexpr int PF(int u) { return (3 * u + 1) / 2; }
-__host__ __device__ constexpr int PH(int u) { return 1 + 3 * (u / 2); }
-__host__ __device__ constexpr int pos(int u, int v) { return v < 4 ? 4 * PF(u) + v : 4 * PH(u) + 2 * (u & 1) + (v - 4); }
-
 struct Geo4h {
     int np;         // 8x32 patches per sample
     int total;      // items = B * np * ncob
 };
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_shr(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_sum16(float v) {  // lane 15 of each 16-lane row ends with the row's total
-    v += dpp_row_shr<0x111>(v);
-    v += dpp_row_shr<0x112>(v);
-    v += dpp_row_shr<0x114>(v);
-    v += dpp_row_shr<0x118>(v);
-    return v;
-}
-
-// a wave-uniform pointer pinned to scalar registers (a resource base left in VGPRs costs a waterfall loop per buffer load)
-__device__ __forceinline__ const float* scalar_ptr(const float* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void bt6(const float (&x)[6], float (&o)[6]) {  // one 6-point input transform B^T x
-    o[0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
-    const float p = __builtin_fmaf(-4.f, x[2], x[4]), q = __builtin_fmaf(-4.f, x[1], x[3]);
-    o[1] = p + q;
-    o[2] = p - q;
-    const float c = x[4] - x[2], e = x[3] - x[1];
-    o[3] = __builtin_fmaf(2.f, e, c);
-    o[4] = __builtin_fmaf(-2.f, e, c);
-    o[5] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]));
-}
-__device__ __forceinline__ void at6(const float x0, const float x1, const float x2, const float x3, const float x4, const float x5, float (&o)[4]) {
-    const float s1 = x1 + x2, d1 = x1 - x2, s2 = x3 + x4, d2 = x3 - x4;  // one 6 -> 4 output transform A^T x
-    o[0] = (x0 + s1) + s2;
-    o[1] = __builtin_fmaf(2.f, d2, d1);
-    o[2] = __builtin_fmaf(4.f, s2, s1);
-    o[3] = __builtin_fmaf(8.f, d2, d1) + x5;
-}
 
 // SPEC: 1 = single source, no prologue; 2 = single source + GN/FiLM/SiLU prologue; 3 = two sources (virtual concat)
 // RAG: the image is not a multiple of the 8x32 patch (tiles outside it are masked)
@@ -161,22 +117,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         rsu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(scalar_ptr(a.wwino4 + (long long)cob * U_FLOATS)), 0, 0x7fffffff, RSRC_FLAGS);
         rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(scalar_ptr(a.src0 + (long long)it_b * a.bs0)), 0, 0x7fffffff, RSRC_FLAGS);
         rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(scalar_ptr(SPEC == 3 ? a.src1 + (long long)it_b * a.bs1 : a.src0)), 0, 0x7fffffff, RSRC_FLAGS);
-        int t = tid;
-        asm volatile("" : "+v"(t));  // opaque: the decode stays here, once per item, instead of hoisted and held in registers
-        omask = 0;
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = t + i * NT;
-            const int ci = e / PSP;
-            const int rem = e - ci * PSP;
-            const int r = rem / RS;
-            const int c = rem - r * RS;
-            const int oy = it_y0 - 1 + r, ox = it_x0 - 1 + c;  // output-grid coordinates of the element
-            const bool in = rem < PS && c < RCOLS && (unsigned)oy < (unsigned)a.Hout && (unsigned)ox < (unsigned)a.Wout;
-            const int sp = MODE == IDIFF_CONV_UPSAMPLE2 ? (oy >> 1) * a.Win + (ox >> 1) : oy * a.Win + ox;
-            gtab[i * NT + tid] = in ? (ci * HWin + sp) * 4 : -1;
-            omask |= (in ? 0u : 1u) << i;
-        }
+        gather_decode<MODE, NT, NL, PSP, PS, RS, RCOLS>(tid, omask, it_y0, it_x0, a, gtab, HWin);
     };
     const int ustride_b = a.ncob * U_FLOATS * 4;  // bytes between chunks of one channel block
 
@@ -485,30 +426,17 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
         hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
         if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4h): hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4h): cannot query the CU count");
-        num_cu = n;
-    }
+    int num_cu = 0;
+    if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4h): cannot query the CU count");
     Geo4h g;
     g.np = a.tiles_x * ((a.Hout + TH - 1) / TH);
     const long long total = (long long)a.B * g.np * a.ncob;
     if (total >= (1ll << 31)) IDIFF_FAIL(IDIFF_E_BADARG, "conv2d(winograd4h): grid too large");
     g.total = (int)total;
-    const int slots = 2 * num_cu;  // two co-resident workgroups per CU
-    const int per = (g.total + slots - 1) / slots;
-    const int grid = (g.total + per - 1) / per;
+    const int grid = persistent_grid(g.total, 2 * num_cu);  // two co-resident workgroups per CU
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a, g);
     IDIFF_CHECK_LAUNCH("conv2d_fwd(winograd4h)");
     return IDIFF_OK;
-}
-
-template <int MODE, int SPEC>
-int launch(const ConvArgs& a, hipStream_t st) {
-    if (a.Hout % TH || a.Wout % TW) return launch_rag<MODE, SPEC, true>(a, st);
-    return launch_rag<MODE, SPEC, false>(a, st);
 }
 
 }  // namespace
@@ -517,10 +445,9 @@ namespace idiff_detail {
 
 // Same shape rules as conv_wino4_eligible (the weight image is the same); the caller has checked those.
 int launch_conv_wino4h(const ConvArgs& a, int mode, hipStream_t st) {
-    if (mode == IDIFF_CONV_UPSAMPLE2) return launch<IDIFF_CONV_UPSAMPLE2, 1>(a, st);
-    if (a.pro_a) return launch<IDIFF_CONV_NORMAL, 2>(a, st);
-    if (a.src1) return launch<IDIFF_CONV_NORMAL, 3>(a, st);
-    return launch<IDIFF_CONV_NORMAL, 1>(a, st);
+    return launch_spec_ladder(mode, a.pro_a != nullptr, a.src1 != nullptr, a.Hout % TH || a.Wout % TW, [&](auto mode_tag, auto spec_tag, auto rag_tag) {
+        return launch_rag<decltype(mode_tag)::value, decltype(spec_tag)::value, decltype(rag_tag)::value>(a, st);
+    });
 }
 
 }  // namespace idiff_detail

@@ -20,11 +20,8 @@
 //   Winograd rows are kept in the forward kernel's order (u0, u1, -u3, u2) on BOTH operands and column 3 is negated on
 //   both, which makes the two wave roles of each transform arithmetically identical and removes every negation; the
 //   products, and therefore M, are unchanged.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "conv_wgrad_args.h"
+#include "wino_common.h"
 
 using idiff_detail::WwArgs;
 
@@ -331,20 +328,12 @@ int launch(const WwArgs& a, hipStream_t st) {
     return IDIFF_OK;
 }
 
-bool wino_wgrad_disabled() {
-    static const bool off = [] {
-        const char* e = getenv("IDIFF_WINOGRAD");
-        return e && e[0] == '0';
-    }();
-    return off;
-}
-
 }  // namespace
 
 namespace idiff_detail {
 
 bool wino_wgrad_eligible(const WwArgs& a, int ks, int mode) {
-    if (ks != 3 || wino_wgrad_disabled()) return false;
+    if (ks != 3 || winograd_disabled()) return false;
     if (mode != IDIFF_CONV_NORMAL && mode != IDIFF_CONV_UPSAMPLE2) return false;
     if (a.Cout % 64 || a.Cin % 16 || a.Hout % 2 || a.Wout % 16) return false;
     if (a.src1 && a.C0v % 64) return false;
