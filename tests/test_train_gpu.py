@@ -349,7 +349,7 @@ def test_unet_param_gradients_and_train_steps_vs_oracle():
     (1, 16, 0, 64, 4, 16, "plain"),           # a single chunk: every edge at once, half a channel block
     (3, 48, 0, 128, 8, 48, "prologue"),       # partial last 32-channel block, two co blocks
     (2, 64, 80, 64, 32, 32, "concat"),        # second source starts on a block boundary; 144 = 4.5 blocks
-    (5, 32, 0, 64, 64, 64, "plain"),          # many chunks per split
+    (5, 32, 0, 64, 64, 64, "plain"),          # 320 chunks on 320 splits: one chunk per split (multi-chunk shares: test_wgrad_wino_gpu.py)
     (3, 48, 0, 128, 8, 24, "upsample"),       # out 16x48: every border chunk kind, partial last channel block
     (2, 32, 0, 64, 2, 8, "upsample"),         # out 4x16: a single chunk per sample
     (2, 32, 0, 64, 6, 16, "upsample"),        # out 12x32: F(4x4) (12 % 4 == 0)

@@ -471,6 +471,8 @@ def test_gn_silu_bwd_film_without_dfilm():
 # 3 / 4 / 5 for Wout < 16 / < 32 / >= 32; THIN for Cout <= 16; CK = 8 for Cin <= 8) and the streaming 1x1 kernel (Cout % 64 == 0,
 # HW % 128 == 0, 16-byte aligned operands).  The Winograd kernels are reached only by shapes none of these rows has (Cout % 64 == 0,
 # Cin % 16 == 0, Wout % 16 == 0), so the direct rows need no environment switch.  Witness: idiff_conv2d_wgrad_last_algo().
+# The Winograd kernels have their own table, wgrad_wino_rows.py (test_wgrad_wino_gpu.py, mirrored on the CPU by test_wgrad_wino_cpu.py):
+# splits that own several chunks, empty splits, prologue-table reloads inside a share, sliced operands, the dY-alignment rungs.
 # =====================================================================================================
 WG_ROWS = [
     # id, B, C0, C1, Cout, Hin, Win, ks, mode, prologue, dy misaligned, accumulate, expected algo, extra channels (src0, src1 and dy are
