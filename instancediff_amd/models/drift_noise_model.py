@@ -7,7 +7,7 @@ test (:648-652), get_visuals/get_nets, save/load file naming `{iter}_{DP,NP,DN,N
 `lastest_*_ema.pth` [sic] (:670-755), save_training_state/resume_training, set_eval/set_train/set_gpu,
 loss-message helpers, learning-rate helpers.
 Changed on purpose:
-  * data parallelism = ONE flat gradient buffer all-reduced over RCCL per step (parallel.FlatGradAllReduce)
+  * data parallelism = the optimizers' flat gradient buffers all-reduced over RCCL, one all-reduce each per step (parallel.GradSync)
     instead of 10 DistributedDataParallel wrappers with find_unused_parameters (:115-146);
   * the 9 per-step `.item()` host syncs (:299-309) become one device->host copy of a 5-float loss record;
   * the 8 dead alternative train steps (:314-629) are not reproduced (out of scope);

@@ -7,8 +7,8 @@ import torch
 from ... import ops
 from .MSM_degEmb_Unet import branch_gains
 from ...train_ops import (ActFn, AddFn, AddVecFn, BLayerNormFn, BLinear3Fn, BLinearFn, BgemmFn, ChanLayerNormFn, ChanNormalizeFn, CompactMemFn,
-                          ConvFn, GatherChannelFn, HeadFoldFn, HeadFoldInLFn, HeadFoldOutLFn, JoinFn, LayerNormRowsFn, Linear3Fn, LinearFn,
-                          ResBlockFn, ScaleColsFn, SkipCatFn, SmmXattnFn, SoftmaxRowsFn, StackFn, StackParamsFn, StackRowsFn, TokenAttnFn,
+                          ConvFn, GatherChannelFn, HeadFoldInFn, HeadFoldOutFn, JoinFn, LayerNormRowsFn, Linear3Fn, LinearFn, ResBlockFn,
+                          ScaleColsFn, SharedGrad, SkipCatFn, SmmXattnFn, SoftmaxRowsFn, StackFn, StackParamsFn, StackRowsFn, TokenAttnFn,
                           UnstackFn, _Slot, dropout, fork)
 
 
@@ -121,49 +121,92 @@ def _self_attention(sa, x, vec=None):
     return AddVecFn.apply(y, vec) if vec is not None else y
 
 
+def _smm_memory(dec, feat, K):
+    """What a ScoreMapModule's cross-attentions attend to -> (mem [B, Cm, N], mem_grad, fused_x, Cm, pts, b2rows).
+    compact (64-channel levels): the (C + 1)-row pre-image of the memory (72 rows instead of 256), with two handles on P^T (pts) and
+    one on the memory LayerNorm's bias row (b2rows) per decoder layer, for _xattn_fold; otherwise the materialised Wd-row memory
+    (LayerNorm -> 1x1 conv -> LayerNorm) and pts = b2rows = None.  mem_grad: the layers' gradients w.r.t. the shared memory are
+    summed inside the fused backward kernel (SmmXattnFn)."""
+    B, C, H, W = feat.shape
+    N, Wd, nlayers = H * W, dec.width, len(dec.decoder)
+    mp = dec.memory_proj
+    fused_x = FUSED_XATTN and dec.heads * K <= 32 and Wd == 256 and N % 4 == 0
+    if TRAIN_COMPACT and fused_x and C == 64 and feat.is_cuda:
+        Cm = 72
+        pts, gram, hvec, evar = _memory_fold(mp, Cm, 2 * nlayers)
+        b2rows = list(fork(mp[2].bias[None, :], nlayers))  # a parameter with several consumers is forked too (no ATen accumulate)
+        mem = CompactMemFn.apply(feat, mp[0].weight, mp[0].bias, gram, hvec, evar, Cm, mp[0].eps, mp[2].eps)
+        return mem, SharedGrad(), fused_x, Cm, list(pts), b2rows
+    fn = ChanLayerNormFn.apply(feat, mp[0].weight, mp[0].bias, mp[0].eps)
+    m1 = ConvFn.apply(fn, None, mp[1].weight.reshape(Wd, C, 1, 1), mp[1].bias, 1, ops.CONV_NORMAL)
+    mem = ChanLayerNormFn.apply(m1, mp[2].weight, mp[2].bias, mp[2].eps).reshape(B, Wd, N)
+    return mem, SharedGrad(), fused_x, Wd, None, None
+
+
+def _xattn_fold(ca, wv, wp, pts, b2rows, Cm):
+    """compact memory mem = P m + b2: fold P into a cross-attention layer's k / v weights (S = q Wk P m up to a per-row constant;
+    o_256 = P (sum_n p_n m_n) + b2).  wv: two handles on ca.v_proj.weight, wp: one on ca.proj.weight (the callers' forks)
+    -> (Wk P [Wd, Cm], Wv P [Wd, Cm], the output projection's bias with b2 Wv^T carried through it [1, Wd])"""
+    Wd = wv[0].shape[0]
+    wkf = BgemmFn.apply(ca.k_proj.weight[None], pts.pop()[None], False, True).reshape(Wd, Cm)   # Wk P
+    wvp = BgemmFn.apply(wv[0][None], pts.pop()[None], False, True).reshape(Wd, Cm)              # Wv P
+    bvf = LinearFn.apply(b2rows.pop(), wv[1], None)                 # b2 Wv^T [1, Wd]: the softmax weights sum to 1
+    return wkf, wvp, LinearFn.apply(bvf, wp, ca.proj.bias)          # ... carried through the output projection
+
+
+def _xattn(qf, mem, scale, fused_x, mem_grad):
+    """softmax(scale qf mem) mem^T over the memory: qf [B, K*heads, Cm] (all heads' query rows stacked, so `mem` is read once per
+    product, not once per head), mem [B, Cm, N]"""
+    if fused_x:
+        return SmmXattnFn.apply(qf, mem, scale, mem_grad)            # one fused forward, one fused backward pass over the keys
+    s_ = BgemmFn.apply(qf, mem, False, False)                        # [B, K*heads, N]
+    return BgemmFn.apply(SoftmaxRowsFn.apply(s_, scale), mem, False, True)
+
+
+def _smm_head(smm, x, t2d_v, feat_n, idx, B, K):
+    """the module's head on the decoder's token rows x [B*K, Wd]: out_proj, text_to_visual, gamma, both normalisations, the score GEMM
+    and the class pick -> (score [B,K,H,W], sel [B,1,H,W])"""
+    _, C, H, W = feat_n.shape
+    op = smm.context_decoder.out_proj
+    diff = LinearFn.apply(LayerNormRowsFn.apply(x, op[0].weight, op[0].bias, op[0].eps), op[1].weight, op[1].bias)  # [R, C]
+    t2v = LinearFn.apply(t2d_v, smm.text_to_visual.weight, smm.text_to_visual.bias)
+    tv = AddFn.apply(t2v, ScaleColsFn.apply(diff, smm.gamma), 1.0)
+    tvn = ChanNormalizeFn.apply(tv.reshape(B * K, C, 1)).reshape(B, K, C)
+    fnm = ChanNormalizeFn.apply(feat_n).reshape(B, C, H * W)
+    score = BgemmFn.apply(tvn, fnm, False, False).reshape(B, K, H, W)
+    score, score_g = fork(score, 2)  # the embedding conv of the skip and the class pick of the pyramid loss
+    return score, GatherChannelFn.apply(score_g, idx)
+
+
 def _smm(smm, feat, text_encoder, idx, feat_n=None):
     """ScoreMapModule forward in Function form -> (score [B,K,h,w], sel [B,1,h,w]).  feat_n: a second handle on the same feature map
     for the score map's normalisation (the caller's fork: the module reads the map twice)"""
-    B, C, H, W = feat.shape
-    K, N = smm.n_cls, H * W
+    B = feat.shape[0]
+    K = smm.n_cls
     dec = smm.context_decoder
     Wd, heads = dec.width, dec.heads
     dh = Wd // heads
     text = smm.text_embeddings(text_encoder, B)
     t2d = text.reshape(B * K, smm.text_dim)
     t2d, t2d_v = fork(t2d, 2)  # text projection and text_to_visual
-    mp = dec.memory_proj
     if feat_n is None:
         feat, feat_n = fork(feat, 2)  # consumed by the memory projection and by the score map's normalisation
-    fused_x = FUSED_XATTN and heads * K <= 32 and Wd == 256 and N % 4 == 0
-    compact = TRAIN_COMPACT and fused_x and C == 64 and feat.is_cuda
-    if compact:
-        # the (C + 1)-row pre-image of the memory (72 rows instead of 256) and the weights that fold its affine map into the attention
-        Cm = 72
-        pts, gram, hvec, evar = _memory_fold(mp, Cm, 2 * len(dec.decoder))
-        pts = list(pts)
-        b2rows = list(fork(mp[2].bias[None, :], len(dec.decoder)))  # a parameter with several consumers is forked too (no ATen accumulate)
-        mem = CompactMemFn.apply(feat, mp[0].weight, mp[0].bias, gram, hvec, evar, Cm, mp[0].eps, mp[2].eps)
-    else:
-        fn = ChanLayerNormFn.apply(feat, mp[0].weight, mp[0].bias, mp[0].eps)
-        m1 = ConvFn.apply(fn, None, mp[1].weight.reshape(Wd, C, 1, 1), mp[1].bias, 1, ops.CONV_NORMAL)
-        mem = ChanLayerNormFn.apply(m1, mp[2].weight, mp[2].bias, mp[2].eps).reshape(B, Wd, N)
+    mem, mem_grad, fused_x, Cm, pts, b2rows = _smm_memory(dec, feat, K)
     tp = dec.text_proj
     x = LinearFn.apply(LayerNormRowsFn.apply(t2d, tp[0].weight, tp[0].bias, tp[0].eps), tp[1].weight, tp[1].bias)
     R = B * K
     # training-mode dropout of the decoder blocks (TransformerDecoderLayer(dropout=0.1): Attention.proj_drop on both attentions, the
     # MLP's inner Dropout and the block's output Dropout, models/_modified_BiomedCLIP.py:448-478,520-549); identity in eval()
     pd, tr = dec.dropout, smm.training
-    mem_grad = {}  # the layers' gradients w.r.t. the shared memory are summed inside the fused backward kernel (SmmXattnFn)
     fused_t = K <= 8 and dh <= 64  # few-token self-attention: one fused forward / backward launch each
 
     def branch(y, g):  # TransformerDecoderLayer_scaled's per-channel gain on a residual branch (:586-589); plain layers: none
         return y if g is None else ScaleColsFn.apply(y, g)
 
     # Token rows r = (sample, class token).  No tensor is permuted or copied between the launches: the head dimension of the folded k / v
-    # projections lives in the strides of the batched GEMMs (HeadFoldFn: rows of a sample ordered (token, head) -- the attention over
-    # the memory treats its query rows independently), the three self-attention projections share one packed buffer, and a state
-    # with two consumers (residual + LayerNorm) is forked, so its two gradients meet in one library launch.
+    # projections lives in the strides of the batched GEMMs (HeadFoldInFn / HeadFoldOutFn: rows of a sample ordered (token, head) -- the
+    # attention over the memory treats its query rows independently), the three self-attention projections share one packed buffer,
+    # and a state with two consumers (residual + LayerNorm) is forked, so its two gradients meet in one library launch.
     for layer in dec.decoder:
         sa, ca = layer.self_attn, layer.cross_attn
         g_sa, g_ca, g_mlp = branch_gains(layer)
@@ -181,44 +224,23 @@ def _smm(smm, feat, text_encoder, idx, feat_n=None):
         x, xr = fork(x, 2)
         n2 = LayerNormRowsFn.apply(x, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
         qc = LinearFn.apply(n2, ca.q_proj.weight, None)  # [R, Wd]
-        # k/v projections folded onto the queries: qf_h = q_h Wk_h ; S = qf mem ; o = P mem^T ; av_h = o_h Wv_h^T.
-        # All heads' query rows are stacked ([B, K*heads, Wd]) so `mem` is read once per product, not once per head.
-        if compact:
-            # mem = P m + b2: fold P into the k / v weights (S = q Wk P m up to a per-row constant; o_256 = P (sum_n p_n m_n) + b2)
-            wv_a, wv_b = fork(ca.v_proj.weight, 2)
-            wp_a, wp_b = fork(ca.proj.weight, 2)
-            wkf = BgemmFn.apply(ca.k_proj.weight[None], pts.pop()[None], False, True).reshape(Wd, Cm)   # Wk P
-            wvp = BgemmFn.apply(wv_a[None], pts.pop()[None], False, True).reshape(Wd, Cm)               # Wv P
-            bvf = LinearFn.apply(b2rows.pop(), wv_b, None)                                 # b2 Wv^T [1, Wd]: the softmax weights sum to 1
-            pbias = LinearFn.apply(bvf, wp_a, ca.proj.bias).reshape(Wd)                    # ... carried through the output projection
-            qf = HeadFoldFn.apply(qc, wkf, heads, "in").reshape(B, K * heads, Cm)          # row = k*heads + h
-            o = SmmXattnFn.apply(qf, mem, ca.scale, mem_grad)
-            av = HeadFoldFn.apply(o.reshape(R, heads, Cm), wvp, heads, "out")              # [R, Wd]
-            x = AddFn.apply(xr, branch(dropout(LinearFn.apply(av, wp_b, pbias), pd, tr), g_ca), 1.0)
+        # k/v projections folded onto the queries: qf_h = q_h Wk_h ; S = qf mem ; o = P mem^T ; av_h = o_h Wv_h^T
+        if pts is not None:
+            wv = fork(ca.v_proj.weight, 2)
+            wp_a, wp = fork(ca.proj.weight, 2)
+            wkf, wvp, pbias = _xattn_fold(ca, wv, wp_a, pts, b2rows, Cm)
+            pbias = pbias.reshape(Wd)
         else:
-            qf = HeadFoldFn.apply(qc, ca.k_proj.weight, heads, "in").reshape(B, K * heads, Wd)   # row = k*heads + h
-            if fused_x:
-                o = SmmXattnFn.apply(qf, mem, ca.scale, mem_grad)        # one fused forward, one fused backward pass over the keys
-            else:
-                s_ = BgemmFn.apply(qf, mem, False, False)                # [B, K*heads, N]
-                p = SoftmaxRowsFn.apply(s_, ca.scale)
-                o = BgemmFn.apply(p, mem, False, True)                   # [B, K*heads, Wd]
-            av = HeadFoldFn.apply(o.reshape(R, heads, Wd), ca.v_proj.weight, heads, "out")       # [R, Wd]
-            x = AddFn.apply(xr, branch(dropout(LinearFn.apply(av, ca.proj.weight, ca.proj.bias), pd, tr), g_ca), 1.0)
+            wkf, wvp, wp, pbias = ca.k_proj.weight, ca.v_proj.weight, ca.proj.weight, ca.proj.bias
+        qf = HeadFoldInFn.apply(qc, wkf, heads).reshape(B, K * heads, Cm)              # row = k*heads + h
+        o = _xattn(qf, mem, ca.scale, fused_x, mem_grad)
+        av = HeadFoldOutFn.apply(o.reshape(R, heads, Cm), wvp, heads)                  # [R, Wd]
+        x = AddFn.apply(xr, branch(dropout(LinearFn.apply(av, wp, pbias), pd, tr), g_ca), 1.0)
         x, xr = fork(x, 2)
         n3 = LayerNormRowsFn.apply(x, layer.norm3.weight, layer.norm3.bias, layer.norm3.eps)
         hm = dropout(ActFn.apply(LinearFn.apply(n3, layer.mlp[0].weight, layer.mlp[0].bias), ops.ACT_GELU), pd, tr)
         x = AddFn.apply(xr, branch(dropout(LinearFn.apply(hm, layer.mlp[3].weight, layer.mlp[3].bias), pd, tr), g_mlp), 1.0)
-    op = dec.out_proj
-    diff = LinearFn.apply(LayerNormRowsFn.apply(x, op[0].weight, op[0].bias, op[0].eps), op[1].weight, op[1].bias)  # [R, C]
-    t2v = LinearFn.apply(t2d_v, smm.text_to_visual.weight, smm.text_to_visual.bias)
-    tv = AddFn.apply(t2v, ScaleColsFn.apply(diff, smm.gamma), 1.0)
-    tvn = ChanNormalizeFn.apply(tv.reshape(R, C, 1)).reshape(B, K, C)
-    fnm = ChanNormalizeFn.apply(feat_n).reshape(B, C, N)
-    score = BgemmFn.apply(tvn, fnm, False, False).reshape(B, K, H, W)
-    score, score_g = fork(score, 2)  # the embedding conv of the skip and the class pick of the pyramid loss
-    sel = GatherChannelFn.apply(score_g, idx)
-    return score, sel
+    return _smm_head(smm, x, t2d_v, feat_n, idx, B, K)
 
 
 def _skip_with_embedding(net, i, score, x_skip, skipbuf, din):
@@ -254,31 +276,13 @@ def _smm_all(smms, feats, feats_n, text_encoder, idx):
     L = len(smms)
     decs = [m.context_decoder for m in smms]
     Wd, heads, nlayers = decs[0].width, decs[0].heads, len(decs[0].decoder)
-    dh = Wd // heads
     B = feats[0].shape[0]
     K = smms[0].n_cls
     R = B * K
     pd, tr = decs[0].dropout, smms[0].training
     dev = feats[0].device
     # ---- per level: memory (+ fold) -------------------------------------------------------------------------------------------
-    lv = []
-    for m, dec, feat in zip(smms, decs, feats):
-        Bc, C, H, W = feat.shape
-        N = H * W
-        mp = dec.memory_proj
-        fused_x = FUSED_XATTN and heads * K <= 32 and Wd == 256 and N % 4 == 0
-        compact = TRAIN_COMPACT and fused_x and C == 64
-        e = dict(C=C, N=N, H=H, W=W, fused_x=fused_x, compact=compact, Cm=72 if compact else Wd, mem_grad={}, mp=mp)
-        if compact:
-            pts, gram, hvec, evar = _memory_fold(mp, 72, 2 * nlayers)
-            e["pts"] = list(pts)
-            e["b2rows"] = list(fork(mp[2].bias[None, :], nlayers))
-            e["mem"] = CompactMemFn.apply(feat, mp[0].weight, mp[0].bias, gram, hvec, evar, 72, mp[0].eps, mp[2].eps)
-        else:
-            fn = ChanLayerNormFn.apply(feat, mp[0].weight, mp[0].bias, mp[0].eps)
-            m1 = ConvFn.apply(fn, None, mp[1].weight.reshape(Wd, C, 1, 1), mp[1].bias, 1, ops.CONV_NORMAL)
-            e["mem"] = ChanLayerNormFn.apply(m1, mp[2].weight, mp[2].bias, mp[2].eps).reshape(B, Wd, N)
-        lv.append(e)
+    lv = [_smm_memory(dec, feat, K) for dec, feat in zip(decs, feats)]   # (mem, mem_grad, fused_x, Cm, pts, b2rows)
     # ---- stacked parameters: one gather launch ---------------------------------------------------------------------------------
     kinds, flat = [], []
 
@@ -297,8 +301,8 @@ def _smm_all(smms, feats, feats_n, text_encoder, idx):
         add(f"{li}.n2g", [l.norm2.weight for l in lay]), add(f"{li}.n2b", [l.norm2.bias for l in lay])
         add(f"{li}.wqc", [l.cross_attn.q_proj.weight for l in lay])
         hs_, rest = [], []
-        for l, e in zip(lay, lv):
-            if e["compact"]:
+        for l, (_, _, _, _, pts, _) in zip(lay, lv):
+            if pts is not None:  # a compact level
                 a, b_ = fork(l.cross_attn.proj.weight, 2)
                 hs_.append(a), rest.append(b_)
             else:
@@ -329,26 +333,18 @@ def _smm_all(smms, feats, feats_n, text_encoder, idx):
         QC = BLinearFn.apply(n2, S[f"{li}.wqc"], None)
         with torch.no_grad():
             AV = torch.empty((L, R, Wd), device=dev, dtype=torch.float32)
-        shared_q, avs, pbs = {}, [], []
-        for l, (layer, e) in enumerate(zip(lay, lv)):
+        shared_q, avs, pbs = SharedGrad(), [], []
+        for l, (layer, (mem, mem_grad, fused_x, Cm, pts, b2rows)) in enumerate(zip(lay, lv)):
             ca = layer.cross_attn
-            Cm = e["Cm"]
-            if e["compact"]:
-                wv_a, wv_b = fork(ca.v_proj.weight, 2)
-                wkf = BgemmFn.apply(ca.k_proj.weight[None], e["pts"].pop()[None], False, True).reshape(Wd, Cm)   # Wk P
-                wvp = BgemmFn.apply(wv_a[None], e["pts"].pop()[None], False, True).reshape(Wd, Cm)               # Wv P
-                bvf = LinearFn.apply(e["b2rows"].pop(), wv_b, None)                                 # b2 Wv^T
-                pbs.append(LinearFn.apply(bvf, proj_w_rest[li][l], ca.proj.bias))                   # ... through the output projection [1, Wd]
+            if pts is not None:
+                wkf, wvp, pb = _xattn_fold(ca, fork(ca.v_proj.weight, 2), proj_w_rest[li][l], pts, b2rows, Cm)
+                pbs.append(pb)
             else:
                 wkf, wvp = ca.k_proj.weight, ca.v_proj.weight
                 pbs.append(ca.proj.bias[None, :])
-            qf = HeadFoldInLFn.apply(QC, wkf, heads, l, shared_q).reshape(B, K * heads, Cm)        # row = k*heads + h
-            if e["fused_x"]:
-                o = SmmXattnFn.apply(qf, e["mem"], ca.scale, e["mem_grad"])
-            else:
-                s_ = BgemmFn.apply(qf, e["mem"], False, False)
-                o = BgemmFn.apply(SoftmaxRowsFn.apply(s_, ca.scale), e["mem"], False, True)
-            avs.append(HeadFoldOutLFn.apply(o.reshape(R, heads, Cm), wvp, heads, _Slot(AV[l].detach())))
+            qf = HeadFoldInFn.apply(QC, wkf, heads, l, shared_q).reshape(B, K * heads, Cm)          # row = k*heads + h
+            o = _xattn(qf, mem, ca.scale, fused_x, mem_grad)
+            avs.append(HeadFoldOutFn.apply(o.reshape(R, heads, Cm), wvp, heads, _Slot(AV[l].detach())))
         AVs = JoinFn.apply(_Slot(AV), *avs)
         PB = StackFn.apply(*pbs).reshape(L, Wd)
         X = AddFn.apply(Xr, dropout(BLinearFn.apply(AVs, S[f"{li}.wpc"], PB), pd, tr), 1.0)
@@ -358,19 +354,7 @@ def _smm_all(smms, feats, feats_n, text_encoder, idx):
         X = AddFn.apply(Xr, dropout(BLinearFn.apply(hm, S[f"{li}.w3"], S[f"{li}.b3"]), pd, tr), 1.0)
     xs = UnstackFn.apply(X)
     # ---- per level: the module's head ------------------------------------------------------------------------------------------
-    outs = []
-    for m, dec, e, x, t2d, fn_ in zip(smms, decs, lv, xs, t2vs_in, feats_n):
-        C, H, W, N = e["C"], e["H"], e["W"], e["N"]
-        op = dec.out_proj
-        diff = LinearFn.apply(LayerNormRowsFn.apply(x, op[0].weight, op[0].bias, op[0].eps), op[1].weight, op[1].bias)  # [R, C]
-        t2v = LinearFn.apply(t2d, m.text_to_visual.weight, m.text_to_visual.bias)
-        tv = AddFn.apply(t2v, ScaleColsFn.apply(diff, m.gamma), 1.0)
-        tvn = ChanNormalizeFn.apply(tv.reshape(R, C, 1)).reshape(B, K, C)
-        fnm = ChanNormalizeFn.apply(fn_).reshape(B, C, N)
-        score = BgemmFn.apply(tvn, fnm, False, False).reshape(B, K, H, W)
-        score, score_g = fork(score, 2)
-        outs.append((score, GatherChannelFn.apply(score_g, idx)))
-    return outs
+    return [_smm_head(m, x, t2d, fn_, idx, B, K) for m, x, t2d, fn_ in zip(smms, xs, t2vs_in, feats_n)]
 
 
 def forward_train(net, x_a, x_b, t, names, text_encoder, image_context=None):

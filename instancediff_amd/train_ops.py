@@ -308,11 +308,54 @@ class BgemmFn(torch.autograd.Function):
         return dA, dB, None, None, None
 
 
+class SharedGrad:
+    """Several autograd nodes that write ONE gradient buffer between them (the decoder layers' cross-attentions summing into the
+    gradient of the memory they all read; the L levels' fold-ins each writing its slice of the stacked queries' gradient): the last
+    of them to run hands the buffer to autograd, the others return None -- no adds between them.  One object per sharing group and
+    forward pass; every node enters in its forward and leaves in its backward.  Single use: one backward per forward.  A second
+    backward over a retained graph would hand the buffer out again, or never, so it raises."""
+    __slots__ = ("pending", "buf")
+
+    def __init__(self):
+        self.pending, self.buf = 0, None
+
+    def enter(self):
+        if self.pending == 0 and self.buf is not None:
+            raise RuntimeError("SharedGrad: a shared gradient buffer is still held from an unfinished backward")
+        self.pending += 1
+
+    def leave(self, like):
+        """-> (the group's buffer, shaped like `like`; whether an earlier backward of the group has written it).  The caller writes
+        its part and returns result() to autograd."""
+        if self.pending == 0:
+            self.buf = None
+            raise RuntimeError("SharedGrad: more backward than forward calls on a shared gradient (retain_graph / double backward is "
+                               "not supported by the shared-gradient form)")
+        self.pending -= 1
+        held = self.buf is not None
+        if not held:
+            self.buf = torch.empty_like(like)
+        return self.buf, held
+
+    def result(self):
+        """the buffer from the last node of the group to run, None from the others (it is still being written)"""
+        if self.pending > 0:
+            return None
+        buf, self.buf = self.buf, None
+        return buf
+
+
 # ---- stacked token chains (r05): the same layer of a net's four ScoreMapModule decoders as ONE batch-L launch ----------------------
+def stack_params_key(L, nk, params):
+    """what StackParamsFn's segment table depends on: the split, the device and every parameter's address AND size (the caching
+    allocator hands a freed address to tensors of other sizes)"""
+    return (L, nk, params[0].device) + tuple((p.data_ptr(), p.numel()) for p in params)
+
+
 class StackParamsFn(torch.autograd.Function):
     """nk kinds x L levels of parameter tensors (kind-major: kind k of level l at index k*L + l; the L tensors of a kind share their
-    shape) -> nk stacked [L, *shape] tensors, gathered by ONE launch (idiff_gather_segments; the segment table is built once per set
-    of addresses and stays on the device).  Backward hands every parameter the view dstack_k[l] -- no copy."""
+    shape) -> nk stacked [L, *shape] tensors, gathered by ONE launch (idiff_gather_segments; the segment table is built once per
+    stack_params_key and stays on the device).  Backward hands every parameter the view dstack_k[l] -- no copy."""
     _tables = {}
 
     @staticmethod
@@ -330,7 +373,7 @@ class StackParamsFn(torch.autograd.Function):
             sizes.append(params[k * L].numel())
         total = L * sum(sizes)
         flat = torch.empty((total,), device=dev, dtype=torch.float32)
-        key = tuple(p.data_ptr() for p in params)
+        key = stack_params_key(L, nk, params)
         hit = StackParamsFn._tables.get(key)
         if hit is None:
             tab = np.zeros((L * nk, 4), dtype=np.int64)
@@ -515,74 +558,6 @@ class BLayerNormFn(torch.autograd.Function):
         return dx, dg, db, None
 
 
-class HeadFoldInLFn(torch.autograd.Function):
-    """HeadFoldFn "in" for level l of a STACKED query matrix xq [L, R, heads*dh] (read in place); the L calls of a layer share the
-    gradient buffer dxq: each writes its slice, the last one to run hands it to autograd (the others return None)."""
-
-    @staticmethod
-    def forward(ctx, xq, w, heads, l, shared):
-        w = w.contiguous()
-        L, R, HD = xq.shape
-        Wd = w.shape[1]
-        dh = HD // heads
-        y = torch.empty((R, heads, Wd), device=xq.device, dtype=torch.float32)
-        bgemm(xq[l], w, R, Wd, dh, HD, Wd, False, False, dh, dh * Wd, heads, out=y, ldc=heads * Wd, sC=Wd)
-        ctx.save_for_backward(xq, w)
-        ctx.geom, ctx.shared = (R, Wd, dh, heads, l), shared
-        shared["pending"] = shared.get("pending", 0) + 1
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        xq, w = ctx.saved_tensors
-        R, Wd, dh, heads, l = ctx.geom
-        sh = ctx.shared
-        dy = dy.contiguous()
-        if sh.get("buf") is None:
-            sh["buf"] = torch.empty_like(xq)
-        bgemm(dy, w, R, dh, Wd, heads * Wd, Wd, False, True, Wd, dh * Wd, heads, out=sh["buf"][l], ldc=heads * dh, sC=dh)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            bgemm(xq[l], dy, dh, Wd, R, heads * dh, heads * Wd, True, False, dh, Wd, heads, out=dw, ldc=Wd, sC=dh * Wd)
-        sh["pending"] -= 1
-        if sh["pending"] > 0:
-            return None, dw, None, None, None
-        buf, sh["buf"] = sh["buf"], None
-        return buf, dw, None, None, None
-
-
-class HeadFoldOutLFn(torch.autograd.Function):
-    """HeadFoldFn "out" writing into slot.t (= slice l of a stacked buffer): y[r, h*dh:(h+1)*dh] = x[r, h, :] @ w[h*dh:(h+1)*dh, :]^T"""
-
-    @staticmethod
-    def forward(ctx, x, w, heads, slot):
-        x, w = x.contiguous(), w.contiguous()
-        R = x.shape[0]
-        Wd = w.shape[1]
-        dh = w.shape[0] // heads
-        y = slot.t
-        assert tuple(y.shape) == (R, heads * dh) and y.is_contiguous()
-        bgemm(x, w, R, dh, Wd, heads * Wd, Wd, False, True, Wd, dh * Wd, heads, out=y, ldc=heads * dh, sC=dh)
-        ctx.save_for_backward(x, w)
-        ctx.geom = (R, Wd, dh, heads)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        R, Wd, dh, heads = ctx.geom
-        dy = dy.contiguous()
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            bgemm(dy, w, R, Wd, dh, heads * dh, Wd, False, False, dh, dh * Wd, heads, out=dx, ldc=heads * Wd, sC=Wd)
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            bgemm(dy, x, dh, Wd, R, heads * dh, heads * Wd, True, False, dh, Wd, heads, out=dw, ldc=Wd, sC=dh * Wd)
-        return dx, dw, None, None
-
-
 class StackRowsFn(torch.autograd.Function):
     """[A ; brow ; 0] -> [Cm, n]: the (C + 1) live rows of the compact memory's weight image above zero padding; backward = row slices"""
 
@@ -645,50 +620,85 @@ class CompactMemFn(torch.autograd.Function):
                 dpar[o + 3 * Cc:o + 3 * Cc + 1].reshape(evar.shape), None, None, None)
 
 
-class HeadFoldFn(torch.autograd.Function):
-    """Per-head product between token rows and a weight's head blocks, with the head dimension living in the STRIDES of the batched GEMM
-    (no permute / reshape copies, whose autograd backward is an ATen copy or a zero-fill + add per head):
-      fold = "in":   y[r, h, :] = x[r, h*dh:(h+1)*dh] @ w[h*dh:(h+1)*dh, :]          x [R, heads*dh], w [heads*dh, Wd] -> y [R, heads, Wd]
-      fold = "out":  y[r, h*dh:(h+1)*dh] = x[r, h, :] @ w[h*dh:(h+1)*dh, :]^T        x [R, heads, Wd], w [heads*dh, Wd] -> y [R, heads*dh]
-    (the cross-attention's k / v projections folded onto the class-token queries / outputs; row r = (sample, class token), so
-    y.reshape(B, K*heads, Wd) is the per-sample row block the fused attention kernel takes, rows ordered (token, head))."""
+# ---- head folds: the cross-attention's k / v projections folded onto the class-token queries / outputs ----------------------------
+# Per-head products between token rows and a weight's head blocks w_h = w[h*dh:(h+1)*dh, :] (w [heads*dh, Wd]), with the head
+# dimension living in the STRIDES of the batched GEMM (no permute / reshape copies, whose autograd backward is an ATen copy or a
+# zero-fill + add per head).  Two row layouts: narrow [R, heads*dh] and wide [R, heads, Wd]; g = (R, Wd, dh, heads).  Each index form
+# is written here once: widening is the fold-in and the fold-out's dx, narrowing the fold-out and the fold-in's dx.
+def _fold_widen(nar, w, out, g):
+    """out[r, h, :] = nar[r, h*dh:(h+1)*dh] @ w_h"""
+    R, Wd, dh, heads = g
+    return bgemm(nar, w, R, Wd, dh, heads * dh, Wd, False, False, dh, dh * Wd, heads, out=out, ldc=heads * Wd, sC=Wd)
+
+
+def _fold_narrow(wide, w, out, g):
+    """out[r, h*dh:(h+1)*dh] = wide[r, h, :] @ w_h^T"""
+    R, Wd, dh, heads = g
+    return bgemm(wide, w, R, dh, Wd, heads * Wd, Wd, False, True, Wd, dh * Wd, heads, out=out, ldc=heads * dh, sC=dh)
+
+
+def _fold_dw(nar, wide, w, g):
+    """dw_h [dh, Wd] = nar_h^T [dh, R] wide_h [R, Wd] (either fold: one side is the saved rows, the other the gradient)"""
+    R, Wd, dh, heads = g
+    return bgemm(nar, wide, dh, Wd, R, heads * dh, heads * Wd, True, False, dh, Wd, heads, out=torch.empty_like(w), ldc=Wd, sC=dh * Wd)
+
+
+class HeadFoldInFn(torch.autograd.Function):
+    """y[r, h, :] = x[r, h*dh:(h+1)*dh] @ w_h: x [R, heads*dh], w [heads*dh, Wd] -> y [R, heads, Wd].  Row r = (sample, class token), so
+    y.reshape(B, K*heads, Wd) is the per-sample row block the fused attention kernel takes, rows ordered (token, head).
+    l, shared: x is level l of a STACKED query matrix [L, R, heads*dh], read in place; the L calls of a layer share the gradient
+    buffer (a SharedGrad): each writes its slice, the last one to run hands it to autograd."""
 
     @staticmethod
-    def forward(ctx, x, w, heads, fold):
-        x, w = x.contiguous(), w.contiguous()
-        R = x.shape[0]
-        Wd = w.shape[1]
-        dh = w.shape[0] // heads
-        ctx.save_for_backward(x, w)
-        ctx.geom = (R, Wd, dh, heads, fold)
-        if fold == "in":
-            y = torch.empty((R, heads, Wd), device=x.device, dtype=torch.float32)
-            bgemm(x, w, R, Wd, dh, heads * dh, Wd, False, False, dh, dh * Wd, heads, out=y, ldc=heads * Wd, sC=Wd)
+    def forward(ctx, x, w, heads, l=None, shared=None):
+        w = w.contiguous()
+        if l is None:
+            x = x.contiguous()
         else:
-            y = torch.empty((R, heads * dh), device=x.device, dtype=torch.float32)
-            bgemm(x, w, R, dh, Wd, heads * Wd, Wd, False, True, Wd, dh * Wd, heads, out=y, ldc=heads * dh, sC=dh)
-        return y
+            shared.enter()
+        rows = x if l is None else x[l]
+        g = ctx.geom = (rows.shape[0], w.shape[1], w.shape[0] // heads, heads)
+        ctx.save_for_backward(x, w)
+        ctx.l, ctx.shared = l, shared
+        return _fold_widen(rows, w, torch.empty((g[0], heads, g[1]), device=x.device, dtype=torch.float32), g)
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        R, Wd, dh, heads, fold = ctx.geom
+        g, l = ctx.geom, ctx.l
         dy = dy.contiguous()
         dx = dw = None
-        if fold == "in":  # y_h = x_h w_h
-            if ctx.needs_input_grad[0]:   # dx_h [R, dh] = dy_h [R, Wd] w_h^T
-                dx = torch.empty_like(x)
-                bgemm(dy, w, R, dh, Wd, heads * Wd, Wd, False, True, Wd, dh * Wd, heads, out=dx, ldc=heads * dh, sC=dh)
-            if ctx.needs_input_grad[1]:   # dw_h [dh, Wd] = x_h^T [dh, R] dy_h [R, Wd]
-                dw = torch.empty_like(w)
-                bgemm(x, dy, dh, Wd, R, heads * dh, heads * Wd, True, False, dh, Wd, heads, out=dw, ldc=Wd, sC=dh * Wd)
-        else:             # y_h = x_h w_h^T
-            if ctx.needs_input_grad[0]:   # dx_h [R, Wd] = dy_h [R, dh] w_h [dh, Wd]
-                dx = torch.empty_like(x)
-                bgemm(dy, w, R, Wd, dh, heads * dh, Wd, False, False, dh, dh * Wd, heads, out=dx, ldc=heads * Wd, sC=Wd)
-            if ctx.needs_input_grad[1]:   # dw_h [dh, Wd] = dy_h^T [dh, R] x_h [R, Wd]
-                dw = torch.empty_like(w)
-                bgemm(dy, x, dh, Wd, R, heads * dh, heads * Wd, True, False, dh, Wd, heads, out=dw, ldc=Wd, sC=dh * Wd)
+        if l is not None:
+            buf, _ = ctx.shared.leave(x)
+            _fold_narrow(dy, w, buf[l], g)
+            dx = ctx.shared.result()
+        elif ctx.needs_input_grad[0]:
+            dx = _fold_narrow(dy, w, torch.empty_like(x), g)
+        if ctx.needs_input_grad[1]:
+            dw = _fold_dw(x if l is None else x[l], dy, w, g)
+        return dx, dw, None, None, None
+
+
+class HeadFoldOutFn(torch.autograd.Function):
+    """y[r, h*dh:(h+1)*dh] = x[r, h, :] @ w_h^T: x [R, heads, Wd], w [heads*dh, Wd] -> y [R, heads*dh], written into slot.t (a slice
+    of a stacked buffer) where one is given"""
+
+    @staticmethod
+    def forward(ctx, x, w, heads, slot=None):
+        x, w = x.contiguous(), w.contiguous()
+        g = ctx.geom = (x.shape[0], w.shape[1], w.shape[0] // heads, heads)
+        y = torch.empty((g[0], w.shape[0]), device=x.device, dtype=torch.float32) if slot is None else slot.t
+        assert tuple(y.shape) == (g[0], w.shape[0]) and y.is_contiguous()
+        ctx.save_for_backward(x, w)
+        return _fold_narrow(x, w, y, g)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        g = ctx.geom
+        dy = dy.contiguous()
+        dx = _fold_widen(dy, w, torch.empty_like(x), g) if ctx.needs_input_grad[0] else None
+        dw = _fold_dw(dy, x, w, g) if ctx.needs_input_grad[1] else None
         return dx, dw, None, None
 
 
@@ -772,17 +782,15 @@ class SmmXattnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qf, mem, scale, shared=None):
-        """shared: a dict common to the calls that attend to the SAME `mem` (the decoder layers of one ScoreMapModule), created per
-        forward pass; it counts the calls ("pending").  Their memory gradients are then summed inside the backward kernel, in backward order, into
-        one buffer that the last of them to run hands to autograd (the others return None): no [B,256,N] adds between them."""
+        """shared: a SharedGrad common to the calls that attend to the SAME `mem` (the decoder layers of one ScoreMapModule), created
+        per forward pass.  Their memory gradients are then summed inside the backward kernel, in backward order, into one buffer that
+        the last of them to run hands to autograd (the others return None): no [B,256,N] adds between them."""
         lib = _lib.load()
         qf, mem = qf.contiguous(), mem.contiguous()
         _c(qf), _c(mem)
         ctx.shared = shared
         if shared is not None:
-            if shared.get("pending", 0) == 0 and shared.get("buf") is not None:
-                raise RuntimeError("SmmXattnFn: a shared memory-gradient buffer is still held from an unfinished backward")
-            shared["pending"] = shared.get("pending", 0) + 1
+            shared.enter()
         B, R, Cm = qf.shape
         N = mem.shape[2]
         assert Cm in (72, 256) and tuple(mem.shape[:2]) == (B, Cm) and R <= 32   # 72: the compact (C + 1)-row memory of a 64-channel level
@@ -804,29 +812,12 @@ class SmmXattnFn(torch.autograd.Function):
         N = mem.shape[2]
         dqf = torch.empty_like(qf)
         sh = ctx.shared
-        acc = 0
-        if sh is None:
-            dmem = torch.empty_like(mem)
-        else:
-            acc = 1 if sh.get("buf") is not None else 0
-            dmem = sh["buf"] if acc else torch.empty_like(mem)
-            sh["buf"] = dmem
-            sh["pending"] -= 1
-            # single use: one backward per forward (a second backward over a retained graph would hand the summed buffer out
-            # again, or never) -- enforced, not assumed
-            if sh["pending"] < 0:
-                sh["pending"], sh["buf"] = 0, None
-                raise RuntimeError("SmmXattnFn: more backward than forward calls on a shared memory gradient (retain_graph / double "
-                                   "backward is not supported by the shared-gradient form; pass shared=None)")
+        dmem, acc = (torch.empty_like(mem), False) if sh is None else sh.leave(mem)
         ws = torch.empty((lib.idiff_smm_xattn_ws_floats(B, R, 1, Cm, N),), device=qf.device, dtype=torch.float32)
         with _prof("smm_xattn_bwd", 5 * 2.0 * 32 * Cm * N * B):  # S, dP, dqf, do^T P, qf^T G: five [32 x Cm] products per key
-            check(lib.idiff_smm_xattn_cm_bwd(_p(qf), _p(mem), _p(o), _p(lse), _p(d_o), _p(dqf), _p(dmem), acc, _p(ws), B, R, Cm, N, ctx.scale,
+            check(lib.idiff_smm_xattn_cm_bwd(_p(qf), _p(mem), _p(o), _p(lse), _p(d_o), _p(dqf), _p(dmem), int(acc), _p(ws), B, R, Cm, N, ctx.scale,
                                              _stream()), "smm_xattn_cm_bwd")
-        if sh is not None:
-            if sh["pending"] > 0:
-                return dqf, None, None, None   # the sum is still growing: the last call to run returns it
-            sh["buf"] = None
-        return dqf, dmem, None, None
+        return dqf, dmem if sh is None else sh.result(), None, None   # shared: None while the sum is still growing
 
 
 class SoftmaxRowsFn(torch.autograd.Function):

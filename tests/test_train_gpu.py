@@ -717,17 +717,17 @@ def test_fork_sums_the_consumers_gradients_in_one_launch_and_skipcat_shares_a_bu
 
 
 def test_token_side_fused_functions_vs_torch_autograd():
-    """HeadFoldFn (per-head k / v folds with the head dimension in the GEMM strides), Linear3Fn (packed q | k | v projection) and
+    """HeadFoldInFn / HeadFoldOutFn (per-head k / v folds with the head dimension in the GEMM strides), Linear3Fn (packed q | k | v projection) and
     TokenAttnFn (few-token self-attention, one fused backward launch) against torch autograd of the plain formulas in fp64."""
     g = _g(41)
     B, K, heads, Wd = 3, 5, 4, 256
     dh, R = Wd // heads, B * K
-    # HeadFoldFn
+    # HeadFoldInFn / HeadFoldOutFn
     for fold in ("in", "out"):
         x = torch.randn(R, Wd if fold == "in" else heads * Wd, generator=g) * 0.5
         w = torch.randn(Wd, Wd, generator=g) * 0.1
         xd, wd = _leaf(x), _leaf(w)
-        y = T.HeadFoldFn.apply(xd if fold == "in" else xd.reshape(R, heads, Wd), wd, heads, fold)
+        y = T.HeadFoldInFn.apply(xd, wd, heads) if fold == "in" else T.HeadFoldOutFn.apply(xd.reshape(R, heads, Wd), wd, heads)
         up = torch.randn(y.shape, generator=g)
         (y * up.to(DEV)).sum().backward()
         xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
@@ -813,8 +813,8 @@ def test_select_conv_function_vs_conv_then_gather_autograd(B, C, K, H, W):
 
 
 def test_stacked_token_functions_vs_torch_autograd():
-    """BLinearFn / BLinear3Fn / BLayerNormFn / StackParamsFn / StackFn / UnstackFn / JoinFn / HeadFoldInLFn / HeadFoldOutLFn (r05: the
-    token chains of a net's four ScoreMapModule decoders as one stack) against torch autograd of the per-level formulas in fp64."""
+    """BLinearFn / BLinear3Fn / BLayerNormFn / StackParamsFn / StackFn / UnstackFn / JoinFn and the stacked forms of HeadFoldInFn /
+    HeadFoldOutFn (r05: the token chains of a net's four ScoreMapModule decoders as one stack) against torch autograd of the per-level formulas in fp64."""
     g = _g(83)
     L, R, K, N = 4, 15, 40, 24
     xs = [torch.randn(R, K, generator=g) for _ in range(L)]
@@ -856,10 +856,10 @@ def test_stacked_token_functions_vs_torch_autograd():
     wf = [torch.randn(heads * dh, Cm, generator=g) * 0.3 for _ in range(L)]
     upq = torch.randn(L, R, heads * dh, generator=g)
     qd, wfd = _leaf(q), [_leaf(t) for t in wf]
-    shared, AV, parts = {}, torch.empty(L, R, heads * dh, device=DEV), []
+    shared, AV, parts = T.SharedGrad(), torch.empty(L, R, heads * dh, device=DEV), []
     for l in range(L):
-        y = T.HeadFoldInLFn.apply(qd, wfd[l], heads, l, shared)                     # [R, heads, Cm]
-        parts.append(T.HeadFoldOutLFn.apply(y, wfd[l], heads, T._Slot(AV[l].detach())))
+        y = T.HeadFoldInFn.apply(qd, wfd[l], heads, l, shared)                      # [R, heads, Cm]
+        parts.append(T.HeadFoldOutFn.apply(y, wfd[l], heads, T._Slot(AV[l].detach())))
     (T.JoinFn.apply(T._Slot(AV), *parts) * upq.to(DEV)).sum().backward()
     qr = q.double().requires_grad_(True)
     wfr = [t.double().requires_grad_(True) for t in wf]
@@ -872,3 +872,65 @@ def test_stacked_token_functions_vs_torch_autograd():
     assert _rel(qd.grad, qr.grad) < 2e-5
     for l in range(L):
         assert _rel(wfd[l].grad, wfr[l].grad) < 2e-5
+
+
+def test_stacked_fold_in_shared_gradient_raises_on_a_second_backward():
+    """The stacked HeadFoldInFn at the step's geometry (L = 2 levels of B*K = 10 token rows, 4 heads of 64, the compact memory's 72
+    columns): the L calls write their slices of one SharedGrad buffer, checked against torch autograd of the per-level formula in
+    fp64 as in test_stacked_token_functions_vs_torch_autograd; a second backward over the retained graph raises instead of handing
+    out a buffer with one slice written."""
+    g = _g(85)
+    L, B, K, heads, dh, Cm = 2, 2, 5, 4, 64, 72
+    R = B * K
+    q = torch.randn(L, R, heads * dh, generator=g)
+    wf = [torch.randn(heads * dh, Cm, generator=g) * 0.3 for _ in range(L)]
+    up = torch.randn(L, R, heads, Cm, generator=g)
+    qd, wfd = _leaf(q), [_leaf(t) for t in wf]
+    shared = T.SharedGrad()
+    loss = sum((T.HeadFoldInFn.apply(qd, wfd[l], heads, l, shared) * up[l].to(DEV)).sum() for l in range(L))
+    loss.backward(retain_graph=True)
+    qr = q.double().requires_grad_(True)
+    wfr = [t.double().requires_grad_(True) for t in wf]
+    sum((torch.einsum("rhd,hdn->rhn", qr[l].reshape(R, heads, dh), wfr[l].reshape(heads, dh, Cm)) * up[l].double()).sum()
+        for l in range(L)).backward()
+    assert _rel(qd.grad, qr.grad) < 2e-5
+    for l in range(L):
+        assert _rel(wfd[l].grad, wfr[l].grad) < 2e-5
+    with pytest.raises(RuntimeError, match="retain_graph / double backward"):
+        loss.backward()
+
+
+def test_fused_cross_attention_shared_memory_gradient_sums_and_raises_on_a_second_backward():
+    """Two SmmXattnFn calls on one `mem` through one SharedGrad (two decoder layers of a ScoreMapModule): dmem is the sum of both
+    calls' memory gradients, accumulated inside the backward kernel, against fp64 autograd within the 5e-5 of
+    test_fused_scoremap_cross_attention_forward_backward_vs_fp64; a second backward over the retained graph raises."""
+    g = _g(97)
+    B, R, N, Cm, scale = 1, 20, 96, 72, 0.125
+    qfs = [torch.randn(B, R, Cm, generator=g) * 0.3 for _ in range(2)]
+    mem = torch.randn(B, Cm, N, generator=g)
+    dos = [torch.randn(B, R, Cm, generator=g) for _ in range(2)]
+    mem[:, 65:] = 0.0
+    m64 = mem.double().requires_grad_(True)
+    for qf, do in zip(qfs, dos):
+        s = torch.einsum('brc,bcn->brn', qf.double(), m64) * scale
+        torch.einsum('brn,bcn->brc', s.softmax(-1), m64).backward(do.double())
+    md = mem.to(DEV).requires_grad_(True)
+    shared = T.SharedGrad()
+    loss = sum((T.SmmXattnFn.apply(qf.to(DEV).requires_grad_(True), md, scale, shared) * do.to(DEV)).sum() for qf, do in zip(qfs, dos))
+    loss.backward(retain_graph=True)
+    e = float((md.grad.cpu().double() - m64.grad).abs().max() / m64.grad.abs().max())
+    print(f"shared fused cross-attention: dmem rel err {e:.2e}")
+    assert e < 5e-5, e
+    with pytest.raises(RuntimeError, match="retain_graph / double backward"):
+        loss.backward()
+
+
+def test_stack_params_table_cache_tells_equal_addresses_of_other_sizes_apart():
+    """StackParamsFn's segment table is cached under the parameters' addresses AND sizes: two parameter sets at the same addresses
+    (what the caching allocator hands out after a reload) with other sizes each get their own table.  The smaller set comes first, so
+    a stale table would copy too little, never past a buffer."""
+    buf = torch.arange(64, dtype=torch.float32, device=DEV)
+    for rows in (2, 4):
+        views = [buf[o:o + rows * 8].view(rows, 8) for o in (0, 32)]
+        (out,) = T.StackParamsFn.apply(2, 1, *views)
+        assert torch.equal(out, torch.stack(views))
