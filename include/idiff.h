@@ -539,6 +539,37 @@ int idiff_ensemble_order_stats(const float* x, float* out, int B, int S, int64_t
 int idiff_interval_coverage(const float* lo, const float* hi, const float* target, int32_t* counts, int32_t* ws, int B, int64_t n_s,
                             idiff_stream_t stream);
 int64_t idiff_interval_coverage_ws_ints(int B, int64_t n_s);
+/* Ensemble scores: x [B][S][n_s] (the samples of an ensemble), target [B][n_s] -> per image the sums behind the CRPS and
+ * the spread-skill ratio, and the rank histogram of the truth among the members.  Per pixel, members in index order s = 0 .. S-1, every
+ * operation rounded once in fp32, no contraction:
+ *   d_s  = x_s - y
+ *   r_s  = #{ j : d_j < d_s } + #{ j < s : d_j == d_s }              a permutation of 0 .. S-1: ties take the lower rank at the lower index
+ *   a    = ((|d_0| + |d_1|) + |d_2|) + ...
+ *   g    = ((c_0*d_0 + c_1*d_1) + c_2*d_2) + ... ,  c_s = (float)(2 r_s - S + 1)   (exact)
+ *   crps = a / S - g / S^2                                           two correctly rounded quotients, one subtraction
+ *   m    = (((d_0 + d_1) + d_2) + ...) / S ;  e = m*m                squared error of the ensemble mean
+ *   v    = (((d_0 - m)^2 + (d_1 - m)^2) + ...) / (S - 1) ;  v = 0 for S = 1       sample variance
+ *   k    = #{ s : d_s < 0 }                                          rank of the truth, 0 .. S (= #{ x_s < y })
+ * crps is the CRPS of the members' empirical CDF, (1/S) sum |x_s - y| - (1/(2 S^2)) sum sum |x_i - x_j|; since sum c_s = 0 the d_s give
+ * what the x_s would in exact arithmetic, with a well-conditioned signed sum.  A member equal to the truth (d_s == 0, i.e. x_s == y) is
+ * not below it, so the truth takes the lowest rank among its ties.  A pixel is invalid if any d_s is NaN: it adds to no sum and to no
+ * histogram bin, is counted in `invalid`, and crps_map holds NaN there.  Infinite d_s are values: they rank and count, and make that
+ * pixel's terms, and so the image's sums, non-finite.
+ *   sums     float64 [B][3]    = sum crps, sum e, sum v over the valid pixels
+ *   counts   int32 [B][S + 2]  = hist[0 .. S] (pixels per k), then invalid
+ *   crps_map fp32 [B][n_s], or NULL to skip it
+ *   ws       idiff_ensemble_scores_ws_bytes(B, S) bytes, 8-byte aligned
+ * Two launches: 64 blocks per image of 256 threads, one float4 per lane per member, grid-stride; a thread adds its pixels' fp32 crps, e,
+ * v into fp64 in loop order, a fixed shuffle tree per wave, the four waves in index order, one fp64 partial per block and quantity;
+ * the block's histogram is S + 2 int32 bins in LDS (integer LDS adds).  The second launch adds the 64 partials of an image in index order.
+ * No float atomics, no global atomics: the result of image b does not depend on B and is bit-identical from run to run.  For S <= 16 a
+ * thread keeps its S float4 in registers; above that (or with IDIFF_ENSEMBLE_REREAD=1 in the environment) it takes candidates four at a
+ * time and reads the members again; the bits are the same.
+ * n_s % 4 == 0, n_s < 2^31, x / target / crps_map 16-byte aligned, 1 <= B <= 65535, 1 <= S <= 1024, crps_map distinct from x and target,
+ * ws / sums / counts buffers of their own.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_ensemble_scores(const float* x, const float* target, float* crps_map, double* sums, int32_t* counts, void* ws, int B, int S,
+                          int64_t n_s, idiff_stream_t stream);
+int64_t idiff_ensemble_scores_ws_bytes(int B, int S);
 /* ---- tiled sampling (driftSDE tile / tile_overlap) ----
  * The chain's state is one full-resolution image [B][C][H][W]; the nets see it as a batch of ny*nx windows of Ph x Pw per image, window
  * row ((b*ny + iy)*nx + ix), each [C][Ph][Pw] contiguous.  W, Pw and the W origins are multiples of 4; all operands 16-byte aligned.

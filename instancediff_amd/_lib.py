@@ -134,6 +134,8 @@ SIGNATURES = {
     "idiff_ensemble_order_stats": (I, [P, P, I, I, I64, C.POINTER(C.c_int32), I, I, c_stream]),
     "idiff_interval_coverage": (I, [P, P, P, P, P, I, I64, c_stream]),
     "idiff_interval_coverage_ws_ints": (I64, [I, I64]),
+    "idiff_ensemble_scores": (I, [P, P, P, P, P, P, I, I, I64, c_stream]),
+    "idiff_ensemble_scores_ws_bytes": (I64, [I, I]),
     "idiff_tile_gather": (I, [P, P, I, I, I, I, I, I, I, I, P, P, c_stream]),
     "idiff_drift_reverse_step_tiled_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, U64, U64, U64, c_stream]),
     "idiff_step_state_advance": (I, [P, P, I, I, I, c_stream]),

@@ -1308,3 +1308,290 @@ extern "C" int idiff_interval_coverage(const float* lo, const float* hi, const f
     IDIFF_CHECK_LAUNCH("interval_coverage_final");
     return IDIFF_OK;
 }
+
+// ---- posterior ensembles: CRPS, rank histogram and spread-skill sums (the contract is in include/idiff.h) ----
+namespace {
+
+constexpr int SCORE_PARTS = 64;    // partial blocks per image (= COV_PARTS)
+constexpr int SCORE_MAX_S = 1024;  // the block's LDS histogram holds S + 2 <= 1026 bins
+constexpr int SCORE_CH = 4;        // candidates per chunk of the second-read form (= ORD_CH)
+constexpr int SCORE_REG = 16;      // the register form's largest S (= ENS_REG); the dispatch lists its 16 cases
+
+__device__ __forceinline__ double wave_sum_f64(double v) {  // fixed xor tree: every lane ends with the same bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// What a thread carries through its grid-stride loop: the fp64 sums of its valid pixels' fp32 crps, e, v, in loop order.
+struct ScoreAcc {
+    double crps = 0.0, e = 0.0, v = 0.0;
+};
+
+// The end of a pixel: a, g, ss as in the contract, e = m*m already formed by the caller.  The quotients are IEEE fp32 divisions (S, S^2 <=
+// 2^20 and S - 1 are exact floats), correctly rounded like the fp64 route of ensemble_stats_kernel.  Invalid (a NaN d_s): NaN in the
+// map, bin S + 1, nothing added.  k <= S by construction, so the LDS index stays inside hist[S + 2] whatever the data.
+__device__ __forceinline__ float score_pixel(float a, float g, float ss, float ev, int k, bool bad, int S, ScoreAcc& acc, int* hist) {
+    const float crps = __fsub_rn(__fdiv_rn(a, (float)S), __fdiv_rn(g, (float)(S * S)));
+    const float var = S > 1 ? __fdiv_rn(ss, (float)(S - 1)) : 0.f;
+    atomicAdd(&hist[bad ? S + 1 : k], 1);  // integer LDS add: order-independent
+    if (bad) return __builtin_nanf("");
+    acc.crps += (double)crps;
+    acc.e += (double)ev;
+    acc.v += (double)var;
+    return crps;
+}
+
+__device__ __forceinline__ void score_block_begin(int* hist, int S) {
+    for (int i = threadIdx.x; i < S + 2; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+}
+
+// Wave tree, then the four waves in index order; one fp64 partial per quantity and block, and the block's histogram beside it.
+__device__ __forceinline__ void score_block_end(const ScoreAcc& acc, const int* hist, double (&red)[3][4], double* __restrict__ part_sums,
+                                                int32_t* __restrict__ part_hist, int S) {
+    const double c = wave_sum_f64(acc.crps), e = wave_sum_f64(acc.e), v = wave_sum_f64(acc.v);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = c;
+        red[1][threadIdx.x >> 6] = e;
+        red[2][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();  // also: every LDS add of the block has landed
+    const long long blk = (long long)blockIdx.y * SCORE_PARTS + blockIdx.x;
+    if (threadIdx.x < 3) part_sums[blk * 3 + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+    for (int i = threadIdx.x; i < S + 2; i += blockDim.x) part_hist[blk * (S + 2) + i] = hist[i];
+}
+
+// Register form, S <= 16, one instantiation per S: a thread's S float4 of d_s = x_s - y stay in registers (constant indices only), and
+// the S rank counters of one element at a time.  Each unordered pair (j < s) is compared once: le = d_j <= d_s puts j below s, !le puts s
+// below j (no NaN on a valid pixel), so rank_s = (S - 1 - s) + sum_{j < s} le(j, s) - sum_{t > s} le(s, t): S (S - 1)/2 compares per
+// element, each a v_cmp and two add / subtract-with-carry.  Up to S = 12 the kernel is held to 128 VGPRs, so that four waves per SIMD
+// -- the 64-block grids of 16 images at once -- are resident; S = 16 takes 147 (three waves); no instantiation uses scratch.
+template <int S>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S <= 12 ? 4 : 3))) void ensemble_scores_reg_kernel(
+    const float* __restrict__ x, const float* __restrict__ tgt, float* __restrict__ map, double* __restrict__ part_sums,
+    int32_t* __restrict__ part_hist, long long Q) {
+    __shared__ int hist[SCORE_MAX_S + 2];
+    __shared__ double red[3][4];
+    score_block_begin(hist, S);
+    const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (long long)blockIdx.y * S * Q;
+    const floatx4* t4 = reinterpret_cast<const floatx4*>(tgt) + (long long)blockIdx.y * Q;
+    floatx4* m4 = map ? reinterpret_cast<floatx4*>(map) + (long long)blockIdx.y * Q : nullptr;
+    ScoreAcc acc;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        const floatx4 y = t4[v];
+        floatx4 d[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const floatx4 xv = xs[(long long)s * Q + v];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[s][e] = __fsub_rn(xv[e], y[e]);
+        }
+        floatx4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a = 0.f, g = 0.f, sd = 0.f, ss = 0.f;
+            int k = 0;
+            bool bad = false;
+            int rank[S];  // one compare per unordered pair: le puts j below s, !le puts s below j (no NaN on a valid pixel)
+#pragma unroll
+            for (int s = 0; s < S; ++s) rank[s] = S - 1 - s;
+#pragma unroll
+            for (int s = 1; s < S; ++s)
+#pragma unroll
+                for (int j = 0; j < s; ++j) {
+                    const int le = d[j][e] <= d[s][e] ? 1 : 0;
+                    rank[s] += le;
+                    rank[j] -= le;
+                }
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const float ds = d[s][e];
+                const float term = __fmul_rn((float)(2 * rank[s] - S + 1), ds);
+                bad |= ds != ds;
+                k += ds < 0.f ? 1 : 0;
+                a = s == 0 ? fabsf(ds) : __fadd_rn(a, fabsf(ds));
+                g = s == 0 ? term : __fadd_rn(g, term);
+                sd = s == 0 ? ds : __fadd_rn(sd, ds);
+            }
+            const float m = __fdiv_rn(sd, (float)S);
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const float t = __fsub_rn(d[s][e], m);
+                ss = s == 0 ? __fmul_rn(t, t) : __fadd_rn(ss, __fmul_rn(t, t));
+            }
+            o[e] = score_pixel(a, g, ss, __fmul_rn(m, m), k, bad, S, acc, hist);
+        }
+        if (m4) m4[v] = o;
+    }
+    score_block_end(acc, hist, red, part_sums, part_hist, S);
+}
+
+// Second-read form, any S: one pass over the members for a, the mean and k, then candidates SCORE_CH at a time in index order, each
+// chunk walking all S members again for its ranks (ensemble_order_rank_kernel's compares, on d instead of x; the re-reads hit L2).  g and
+// the squared deviations are added as the chunks finish, i.e. in member order: the same operations in the same order as the register form.
+__global__ __launch_bounds__(256) void ensemble_scores_reread_kernel(const float* __restrict__ x, const float* __restrict__ tgt, float* __restrict__ map,
+                                                                     double* __restrict__ part_sums, int32_t* __restrict__ part_hist, int S, long long Q) {
+    __shared__ int hist[SCORE_MAX_S + 2];
+    __shared__ double red[3][4];
+    score_block_begin(hist, S);
+    const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (long long)blockIdx.y * S * Q;
+    const floatx4* t4 = reinterpret_cast<const floatx4*>(tgt) + (long long)blockIdx.y * Q;
+    floatx4* m4 = map ? reinterpret_cast<floatx4*>(map) + (long long)blockIdx.y * Q : nullptr;
+    ScoreAcc acc;
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < Q; v += (long long)gridDim.x * blockDim.x) {
+        const floatx4 y = t4[v];
+        floatx4 a = {0.f, 0.f, 0.f, 0.f}, g = a, sd = a, ss = a, mv, ev;
+        int k[4] = {0, 0, 0, 0};
+        bool bad[4] = {false, false, false, false};
+        for (int s = 0; s < S; ++s) {
+            const floatx4 xv = xs[(long long)s * Q + v];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ds = __fsub_rn(xv[e], y[e]);
+                bad[e] |= ds != ds;
+                k[e] += ds < 0.f ? 1 : 0;
+                a[e] = s == 0 ? fabsf(ds) : __fadd_rn(a[e], fabsf(ds));
+                sd[e] = s == 0 ? ds : __fadd_rn(sd[e], ds);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            mv[e] = __fdiv_rn(sd[e], (float)S);
+            ev[e] = __fmul_rn(mv[e], mv[e]);
+        }
+        for (int s0 = 0; s0 < S; s0 += SCORE_CH) {
+            floatx4 cand[SCORE_CH];
+            int rank[SCORE_CH][4];
+#pragma unroll
+            for (int c = 0; c < SCORE_CH; ++c) {
+                const int s = s0 + c < S ? s0 + c : S - 1;  // past the end: a copy of the last member, added to nothing
+                const floatx4 xv = xs[(long long)s * Q + v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    cand[c][e] = __fsub_rn(xv[e], y[e]);
+                    rank[c][e] = 0;
+                }
+            }
+            for (int j = 0; j < s0; ++j) {
+                const floatx4 xj = xs[(long long)j * Q + v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float dj = __fsub_rn(xj[e], y[e]);
+#pragma unroll
+                    for (int c = 0; c < SCORE_CH; ++c) rank[c][e] += dj <= cand[c][e] ? 1 : 0;
+                }
+            }
+#pragma unroll
+            for (int jj = 0; jj < SCORE_CH; ++jj)
+                if (s0 + jj < S) {
+#pragma unroll
+                    for (int c = 0; c < SCORE_CH; ++c) {
+                        if (c == jj) continue;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) rank[c][e] += (jj < c ? cand[jj][e] <= cand[c][e] : cand[jj][e] < cand[c][e]) ? 1 : 0;
+                    }
+                }
+            for (int j = s0 + SCORE_CH; j < S; ++j) {
+                const floatx4 xj = xs[(long long)j * Q + v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float dj = __fsub_rn(xj[e], y[e]);
+#pragma unroll
+                    for (int c = 0; c < SCORE_CH; ++c) rank[c][e] += dj < cand[c][e] ? 1 : 0;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < SCORE_CH; ++c)
+                if (s0 + c < S) {
+                    const bool first = s0 + c == 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float term = __fmul_rn((float)(2 * rank[c][e] - S + 1), cand[c][e]);
+                        const float t = __fsub_rn(cand[c][e], mv[e]);
+                        g[e] = first ? term : __fadd_rn(g[e], term);
+                        ss[e] = first ? __fmul_rn(t, t) : __fadd_rn(ss[e], __fmul_rn(t, t));
+                    }
+                }
+        }
+        floatx4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = score_pixel(a[e], g[e], ss[e], ev[e], k[e], bad[e], S, acc, hist);
+        if (m4) m4[v] = o;
+    }
+    score_block_end(acc, hist, red, part_sums, part_hist, S);
+}
+
+// One block per image.  The 3 x SCORE_PARTS fp64 partials are fetched by as many threads at once and added from LDS in index order by
+// one thread per quantity; a bin's integer partials are fetched eight at a time (integer addition: any order gives the same count).
+__global__ __launch_bounds__(256) void ensemble_scores_final_kernel(const double* __restrict__ part_sums, const int32_t* __restrict__ part_hist,
+                                                                    double* __restrict__ sums, int32_t* __restrict__ counts, int S) {
+    __shared__ double part[3][SCORE_PARTS];
+    const long long b = blockIdx.x;
+    if (threadIdx.x < 3 * SCORE_PARTS) {
+        const int q = threadIdx.x / SCORE_PARTS, p = threadIdx.x % SCORE_PARTS;
+        part[q][p] = part_sums[(b * SCORE_PARTS + p) * 3 + q];
+    }
+    for (int i = threadIdx.x; i < S + 2; i += blockDim.x) {
+        const int32_t* col = part_hist + b * SCORE_PARTS * (S + 2) + i;
+        int acc = 0;
+#pragma unroll 8
+        for (int p = 0; p < SCORE_PARTS; ++p) acc += col[(long long)p * (S + 2)];
+        counts[b * (S + 2) + i] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double acc = part[threadIdx.x][0];
+        for (int p = 1; p < SCORE_PARTS; ++p) acc += part[threadIdx.x][p];
+        sums[b * 3 + threadIdx.x] = acc;
+    }
+}
+
+template <int S>
+void launch_scores_reg(const float* x, const float* tgt, float* map, double* ps, int32_t* ph, int B, long long Q, hipStream_t st) {
+    hipLaunchKernelGGL(ensemble_scores_reg_kernel<S>, dim3(SCORE_PARTS, (unsigned)B), dim3(256), 0, st, x, tgt, map, ps, ph, Q);
+}
+
+}  // namespace
+
+extern "C" int64_t idiff_ensemble_scores_ws_bytes(int B, int S) {
+    if (B <= 0 || B > 65535 || S <= 0 || S > SCORE_MAX_S) return 0;
+    return (int64_t)B * SCORE_PARTS * (3 * (int64_t)sizeof(double) + (S + 2) * (int64_t)sizeof(int32_t));
+}
+
+extern "C" int idiff_ensemble_scores(const float* x, const float* target, float* crps_map, double* sums, int32_t* counts, void* ws, int B, int S,
+                                     int64_t n_s, idiff_stream_t stream) {
+    IDIFF_CHECK_ARG(x && target && sums && counts && ws && B > 0 && B <= 65535 && n_s > 0 && n_s <= 0x7fffffffLL, "ensemble_scores: bad args");
+    IDIFF_CHECK_ARG(S >= 1 && S <= SCORE_MAX_S, "ensemble_scores: S = %d is outside [1, %d]", S, SCORE_MAX_S);
+    IDIFF_CHECK_ARG(n_s % 4 == 0, "ensemble_scores: n_s = %lld is not a multiple of 4", (long long)n_s);
+    IDIFF_CHECK_ARG(aligned16({x, target, crps_map}), "ensemble_scores: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG((uintptr_t)sums % 8 == 0 && (uintptr_t)ws % 8 == 0 && (uintptr_t)counts % 4 == 0,
+                    "ensemble_scores: sums and ws must be 8-byte aligned, counts 4-byte aligned");
+    IDIFF_CHECK_ARG(crps_map != x && crps_map != target, "ensemble_scores: crps_map must not be x or target");
+    IDIFF_CHECK_ARG(ws != (void*)sums && ws != (void*)counts && (void*)sums != (void*)counts && ws != (void*)x && ws != (void*)target &&
+                        ws != (void*)crps_map,
+                    "ensemble_scores: ws, sums and counts must be buffers of their own");
+    const long long Q = n_s / 4;
+    hipStream_t st = (hipStream_t)stream;
+    double* ps = static_cast<double*>(ws);
+    int32_t* ph = reinterpret_cast<int32_t*>(ps + (long long)B * SCORE_PARTS * 3);
+    // IDIFF_ENSEMBLE_REREAD=1 (tests): the second-read form also where the values would fit in registers, as in idiff_ensemble_stats
+    const char* rr = getenv("IDIFF_ENSEMBLE_REREAD");
+    if (S > SCORE_REG || (rr && rr[0] == '1')) {
+        hipLaunchKernelGGL(ensemble_scores_reread_kernel, dim3(SCORE_PARTS, (unsigned)B), dim3(256), 0, st, x, target, crps_map, ps, ph, S, Q);
+    } else {
+#define SCORE_CASE(s)                                                   \
+    case s:                                                             \
+        launch_scores_reg<s>(x, target, crps_map, ps, ph, B, Q, st); \
+        break;
+        switch (S) {
+            SCORE_CASE(1) SCORE_CASE(2) SCORE_CASE(3) SCORE_CASE(4) SCORE_CASE(5) SCORE_CASE(6) SCORE_CASE(7) SCORE_CASE(8)
+            SCORE_CASE(9) SCORE_CASE(10) SCORE_CASE(11) SCORE_CASE(12) SCORE_CASE(13) SCORE_CASE(14) SCORE_CASE(15) SCORE_CASE(16)
+        }
+#undef SCORE_CASE
+    }
+    IDIFF_CHECK_LAUNCH("ensemble_scores_partial");
+    hipLaunchKernelGGL(ensemble_scores_final_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)ps, (const int32_t*)ph, sums, counts, S);
+    IDIFF_CHECK_LAUNCH("ensemble_scores_final");
+    return IDIFF_OK;
+}

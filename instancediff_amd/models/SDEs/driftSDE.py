@@ -153,6 +153,40 @@ def order_stat_indices(S, level):
     return dict(k_lo=k_lo, k_hi=k_hi, k_m0=(S - 1) // 2, k_m1=S // 2, nominal=(k_hi - k_lo) / (S + 1))
 
 
+def ensemble_score_summary(sums, counts, S):
+    """The verification scores of an S-member ensemble from what ops.ensemble_scores returns, on the host:
+        sums [..., 3] = sum crps, sum e, sum v;  counts [..., S + 2] = the rank histogram hist[0..S], then the invalid pixels.
+    Rows (images) are pooled first, sums with sums and bins with bins: that is the aggregate over several images, the mean of
+    per-image ratios is not.  ->  dict(
+        N         sum hist: the valid pixels
+        CRPS      sum crps / N
+        SKILL     sqrt(sum e / N): the RMSE of the ensemble mean
+        SPREAD    sqrt((S + 1)/S * sum v / N): the finite-ensemble correction under which a perfectly reliable ensemble has SSR 1
+        SSR       SPREAD / SKILL;  NaN for S = 1 (no spread) or SKILL = 0
+        RANK_DEV  sum_k |hist_k/N - 1/(S + 1)|: 0 for a flat histogram, 2S/(S + 1) when the truth always falls in one bin
+        OUTLIERS  (hist_0 + hist_S)/N, the truth outside every member;  OUTLIERS_nominal = 2/(S + 1)
+        hist      the pooled histogram, ints;  invalid  the pooled invalid count)
+    Every ratio is NaN when N = 0.  Takes tensors, arrays or nested lists."""
+    S = _num_samples(S)
+    sums = torch.as_tensor(sums, dtype=torch.float64).detach().cpu().reshape(-1, 3)
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, S + 2)
+    if sums.shape[0] != counts.shape[0]:
+        raise ValueError(f"ensemble_score_summary: {sums.shape[0]} rows of sums, {counts.shape[0]} rows of counts")
+    tot = [float(t) for t in sums.sum(dim=0)]
+    pooled = [int(c) for c in counts.sum(dim=0)]
+    hist, invalid = pooled[:S + 1], pooled[S + 1]
+    N = sum(hist)
+    nan = float("nan")
+    if N == 0:
+        return dict(N=0, CRPS=nan, SKILL=nan, SPREAD=nan, SSR=nan, RANK_DEV=nan, OUTLIERS=nan, OUTLIERS_nominal=2.0 / (S + 1), hist=hist,
+                    invalid=invalid)
+    skill = math.sqrt(tot[1] / N)
+    spread = math.sqrt((S + 1) / S * tot[2] / N)
+    return dict(N=N, CRPS=tot[0] / N, SKILL=skill, SPREAD=spread, SSR=spread / skill if S > 1 and skill > 0 else nan,
+                RANK_DEV=sum(abs(h / N - 1.0 / (S + 1)) for h in hist), OUTLIERS=(hist[0] + hist[S]) / N, OUTLIERS_nominal=2.0 / (S + 1),
+                hist=hist, invalid=invalid)
+
+
 def _max_batch(rows):
     if not _is_int(rows) or rows < 1:
         raise ValueError(f"driftSDE: max_batch must be an int >= 1, got {rows!r}")
@@ -1007,6 +1041,18 @@ class driftSDE:
         mean, std = ops.ensemble_stats(samples)
         self.last_order_stats = None if self.interval is None else self._order_stats(samples, self.interval)
         return (mean, std, samples) if return_samples else (mean, std)
+
+    @staticmethod
+    def score_ensemble(samples, target, want_map=False):
+        """Ensemble scores of samples [B, S, ...] (reverse_ddpm_ensemble(..., return_samples=True)) against target [B, ...] ->
+        (sums float64 [B, 3], counts int32 [B, S + 2], crps_map [B, ...] or None) on the device, from one ops.ensemble_scores call (two
+        launches, no host copy); ensemble_score_summary(sums, counts, S) reads CRPS / SSR / RANK_DEV / OUTLIERS off them."""
+        if not torch.is_tensor(samples) or samples.dim() < 3:
+            raise ValueError("score_ensemble: samples must be a [B, S, ...] tensor (reverse_ddpm_ensemble(..., return_samples=True))")
+        if not torch.is_tensor(target) or tuple(target.shape) != (samples.shape[0],) + tuple(samples.shape[2:]):
+            raise ValueError(f"score_ensemble: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+        return ops.ensemble_scores(samples.contiguous(), target.contiguous(), want_map=want_map)
 
     @staticmethod
     def _order_stats(samples, level):

@@ -281,6 +281,13 @@ class CLIPDriftModel():
         self.output = out
         self.visuals = out.detach().cpu().numpy()
 
+    def score_ensemble(self, want_map=False):
+        """ensemble scores of the members test(return_samples=True) left in self.samples against self.target (driftSDE.score_ensemble) ->
+        (sums [B, 3], counts [B, S + 2], crps_map or None) on the device"""
+        if getattr(self, "samples", None) is None:
+            raise ValueError("score_ensemble: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        return self.sde.score_ensemble(self.samples, self.target, want_map=want_map)
+
     def get_visuals(self):
         return self.visuals
 

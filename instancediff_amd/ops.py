@@ -936,6 +936,27 @@ def interval_coverage(lo, hi, target):
     return counts
 
 
+def ensemble_scores(x, target, want_map=False):
+    """x [B, S, ...] (the samples of an ensemble), target [B, ...] -> (sums float64 [B, 3], counts int32 [B, S + 2], crps_map [B, ...] or
+    None), all on the device: per image the sums of the per-pixel CRPS, squared error of the ensemble mean and sample variance over the
+    valid pixels; the rank histogram of the truth among the members (hist[0..S]) followed by the number of invalid (NaN) pixels; and,
+    with want_map, the per-pixel CRPS (NaN where invalid).  Two launches, no host copy; include/idiff.h states the arithmetic.
+    models/SDEs/driftSDE.py's ensemble_score_summary turns (pooled) sums and counts into CRPS / SSR / RANK_DEV / OUTLIERS."""
+    lib = _lib.load()
+    _c(x, "x"), _c(target, "target")
+    assert x.dim() >= 3, "ensemble_scores: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    assert tuple(target.shape) == (B,) + tuple(x.shape[2:]), "ensemble_scores: target is x without the member axis"
+    n_s = x.numel() // (B * S) if B * S else 0
+    sums = torch.empty((B, 3), device=x.device, dtype=torch.float64)
+    counts = torch.empty((B, S + 2), device=x.device, dtype=torch.int32)
+    crps_map = torch.empty_like(target) if want_map else None
+    ws = torch.empty((max(int(lib.idiff_ensemble_scores_ws_bytes(B, S)), 8) // 8,), device=x.device, dtype=torch.float64)
+    check(lib.idiff_ensemble_scores(_p(x), _p(target), _p(crps_map), C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                    C.c_void_p(ws.data_ptr()), B, S, n_s, _stream()), "ensemble_scores")
+    return sums, counts, crps_map
+
+
 def plane_sum(x):
     """x [B, C, H, W] -> [B, C]: the sum over the pixels of every plane"""
     lib = _lib.load()

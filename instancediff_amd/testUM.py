@@ -9,12 +9,16 @@ device (:151-164) and writes the LQ|pred|GT `.raw` triptychs (:170-173).  With `
 an S-member posterior ensemble: the metrics and the triptych are the mean's, `PSNR_member` / `STD` and a `<i>_std_WxHx1.raw` map are added.
 With `--interval L` on top of that the per-pixel median and the level-L credible interval of the members are written as `<i>_median_` / `<i>_lo_` /
 `<i>_hi_WxHx1.raw` maps, and `PSNR_median`, `COVER` (the share of ground-truth pixels inside the interval) and `WIDTH` (its mean width) are listed.
+With `--scores` on top of `--num-samples S` the ensemble is verified against the ground truth on the device: `CRPS`, `SSR` (spread-skill ratio) and
+`RANK_DEV` (the rank histogram's distance from flat) are listed per image, a `<i>_crps_WxHx1.raw` map is written, and per artifact type the
+pooled scores are printed and the pooled rank histogram goes to `rank_hist.json`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain.  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
+import json
 import os
 import time
 from collections import OrderedDict
@@ -26,6 +30,7 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
+from .models.SDEs.driftSDE import ensemble_score_summary
 
 
 def main(argv=None):
@@ -45,6 +50,9 @@ def main(argv=None):
     parser.add_argument("--interval", type=float, default=None, metavar="L",
                         help="driftSDE interval: credible level L in (0, 1) of the per-pixel interval and median maps of an ensemble, written "
                              "next to the std map with PSNR_median / COVER / WIDTH (needs num_samples > 1; overrides the YAML)")
+    parser.add_argument("--scores", action="store_true",
+                        help="ensemble scores against the ground truth (needs num_samples > 1): CRPS / SSR / RANK_DEV per image and a CRPS "
+                             "map, the pooled scores and rank_hist.json per artifact type")
     parser.add_argument("--tile", type=int, nargs="+", default=None, metavar="P",
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
@@ -88,6 +96,8 @@ def main(argv=None):
     model.set_sde(sde)
     model.set_eval()
     S = getattr(sde, 'num_samples', 1)
+    if args.scores and S <= 1:
+        parser.error("--scores verifies an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
     result_root = os.path.join(test_opt['result_root'], opt['name'])
     results = OrderedDict((a, {'num': 0, 'RMSE': [], 'SSIM': [], 'PSNR': []}) for a in opt['artifact_type'])
     if S > 1:
@@ -97,6 +107,9 @@ def main(argv=None):
     if level is not None:
         for r in results.values():
             r['PSNR_median'], r['COVER'], r['WIDTH'] = [], [], []
+    if args.scores:
+        for r in results.values():
+            r['CRPS'], r['SSR'], r['RANK_DEV'], r['scores'] = [], [], [], []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -144,6 +157,15 @@ def main(argv=None):
                         m = m[0, 0].cpu()
                         m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_{tag}_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
                     extra += f", PSNR_median={r['PSNR_median'][-1]}, COVER={r['COVER'][-1]}, WIDTH={r['WIDTH'][-1]}"
+                if args.scores:  # CRPS and the spreads on RMSE's x/2 + 0.5 scale: half of what the [-1, 1] tensors give
+                    sums, counts, crps_map = model.score_ensemble(want_map=True)
+                    sums, counts = sums.cpu(), counts.cpu()
+                    one = ensemble_score_summary(sums, counts, S)
+                    r['scores'].append((sums, counts))
+                    r['CRPS'].append(0.5 * one['CRPS']), r['SSR'].append(one['SSR']), r['RANK_DEV'].append(one['RANK_DEV'])
+                    m = crps_map[0, 0].cpu() * 0.5
+                    m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_crps_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
+                    extra += f", CRPS={r['CRPS'][-1]}, SSR={r['SSR'][-1]}, RANK_DEV={r['RANK_DEV'][-1]}"
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -151,7 +173,15 @@ def main(argv=None):
     for k, v in results.items():
         if v['num']:
             print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR') + (('PSNR_member', 'STD') if S > 1 else ())
-                                  + (('PSNR_median', 'COVER', 'WIDTH') if level is not None else ())))
+                                  + (('PSNR_median', 'COVER', 'WIDTH') if level is not None else ()) + (('CRPS',) if args.scores else ())))
+            if args.scores:  # the type's record: sums and histograms pooled over its images, not the mean of the per-image ratios
+                pooled = ensemble_score_summary(torch.cat([s for s, _ in v['scores']]), torch.cat([c for _, c in v['scores']]), S)
+                v['pooled'] = pooled
+                print(f"{k}, pooled over {v['num']} images: CRPS: {0.5 * pooled['CRPS']}, SSR: {pooled['SSR']} (SPREAD {0.5 * pooled['SPREAD']} / SKILL "
+                      f"{0.5 * pooled['SKILL']}), RANK_DEV: {pooled['RANK_DEV']}, OUTLIERS: {pooled['OUTLIERS']} (nominal {pooled['OUTLIERS_nominal']}), "
+                      f"invalid: {pooled['invalid']}")
+                with open(os.path.join(result_root, k, "rank_hist.json"), "w") as f:
+                    json.dump(dict(S=S, hist=pooled['hist'], N=pooled['N'], nominal=1.0 / (S + 1), invalid=pooled['invalid']), f)
     if times:
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
