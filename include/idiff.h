@@ -598,6 +598,25 @@ int idiff_drift_reverse_step_tiled_dev(float* x, const float* r_tiles, const flo
                                        int Pw, const int32_t* ytab, const float* ywt, const int32_t* xtab, const float* xwt, const float* coef,
                                        int coef_rows, int Tp1, const int32_t* state, uint64_t seed, uint64_t nper, uint64_t offset_base,
                                        idiff_stream_t stream);
+/* The step of a tiled chain on the rows of a posterior ensemble (driftSDE tiled_ensemble).  x, cond, r_prev, e_prev are R
+ * full-resolution rows [R][C][H][W], row r one member of one input image (cond per row, as idiff_ensemble_init writes cond_rep); the
+ * window buffers hold row ((r*ny + iy)*nx + ix): idiff_drift_reverse_step_tiled_dev's geometry with B = R.  Per float4 group v of row r
+ * (Q = C*H*W/4 groups per row) the blend, the extrapolation and its zero-rho rule, the update, the hand-over and the scatter are those of
+ * idiff_drift_reverse_step_tiled_dev (one kernel template, one copy of each piece); only z differs:
+ *   z  = z_base[state[2]][r*Q + v] (injected, [steps][R*C*H*W]) or the Philox normals of counter (1 + state[1])*Q + v under member
+ *        members_dev[r]: the draw idiff_drift_reverse_step_members_dev and idiff_randn_members(j = 1 + state[1]) give that member for a
+ *        sample of n_s = C*H*W, whatever the tiling and whatever rows sit beside it.  Nothing is drawn or read where c == 0.
+ * Bit-identity contracts: (1) with z_base, or with device noise against z_base = idiff_randn_members(j = 1 + state[1]), every output
+ * (x, x_tiles, xa_tiles, r_prev, e_prev) equals idiff_drift_reverse_step_tiled_dev's at B = R on the same operands; (2) with one window
+ * (ny = nx = 1, Ph = H, Pw = W) x and xa_tiles equal x and xa of idiff_drift_reverse_step_members_dev on the same operands.
+ * 256 threads, one float4 per lane, grid-stride, grid = (chunks, R); no LDS, no atomics.  Every size and alias check of
+ * idiff_drift_reverse_step_tiled_dev holds with R in place of B, and 0 < R <= 65535, members_dev != NULL, W % 4 == 0, all operands 16-byte
+ * aligned.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_drift_reverse_step_tiled_members_dev(float* x, const float* r_tiles, const float* e_tiles, float* r_prev, float* e_prev,
+                                               const float* z_base, const float* cond, float* x_tiles, float* xa_tiles, int R, int C, int H,
+                                               int W, int ny, int nx, int Ph, int Pw, const int32_t* ytab, const float* ywt,
+                                               const int32_t* xtab, const float* xwt, const float* coef, int coef_rows, int Tp1,
+                                               const int32_t* state, const uint64_t* members_dev, uint64_t seed, idiff_stream_t stream);
 /* t <- t-1 (back to T once t <= t_stop), both counters += 1, tdev[0..B) = (float)t   (the UNets' timestep input) */
 int idiff_step_state_advance(int32_t* state, float* tdev, int B, int T, int t_stop, idiff_stream_t stream);
 /* Few-step schedule form (driftSDE sample_T / sample_timesteps): t <- next_t[t] (back to t_first once t <= t_stop), both counters += 1,

@@ -138,6 +138,7 @@ SIGNATURES = {
     "idiff_ensemble_scores_ws_bytes": (I64, [I, I]),
     "idiff_tile_gather": (I, [P, P, I, I, I, I, I, I, I, I, P, P, c_stream]),
     "idiff_drift_reverse_step_tiled_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, U64, U64, U64, c_stream]),
+    "idiff_drift_reverse_step_tiled_members_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, P, U64, c_stream]),
     "idiff_step_state_advance": (I, [P, P, I, I, I, c_stream]),
     "idiff_step_state_advance_table": (I, [P, P, I, P, I, I, I, c_stream]),
     "idiff_randn": (I, [P, I64, U64, U64, c_stream]),

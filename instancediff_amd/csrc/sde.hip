@@ -629,15 +629,22 @@ __device__ __forceinline__ void blend_slot(const floatx4* __restrict__ src, long
 // (iy1,ix0), (iy1,ix1) in that order, weight wy*wx), extrapolate them when HIST, draw z at the plain chain's counter offset + v,
 // update (the shared pieces above, as drift_step_dev_kernel<HIST>), and scatter x and x - cond into every window whose extent holds
 // the group.  Element-wise per pixel: a thread reads and writes only its own group of x / rp / ep and of each window's copy of it.
-template <bool HIST>
+// MEMBERS is the same step on the rows of an ensemble (idiff_drift_reverse_step_tiled_members_dev): grid = (chunks, R), nv = Q is the
+// groups of ONE row, block row r works on groups r*Q + vl of the R-row image, and its z is drawn as drift_step_members_kernel draws it,
+// from member members[r]'s stream at counter (1 + state[1])*Q + vl; nper and offset_base are not read.  Nothing else differs.
+template <bool HIST, bool MEMBERS>
 __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const float* __restrict__ rt_, const float* __restrict__ et_, float* rp,
                                                                float* ep, const float* __restrict__ zbase, const float* __restrict__ cond,
                                                                float* __restrict__ xt_, float* __restrict__ xat_, long long nv, TileGeom g,
                                                                const float* __restrict__ coef, int Tp1, const int* __restrict__ state,
-                                                               uint64_t seed, uint64_t nper, uint64_t offset_base) {
+                                                               uint64_t seed, uint64_t nper, uint64_t offset_base,
+                                                               const uint64_t* __restrict__ members) {
     const StepCoef k = load_step_coef<HIST>(coef, Tp1, state);
-    const uint64_t offset = offset_base + (uint64_t)(unsigned)state[1] * nper;
-    const floatx4* z4 = zbase ? reinterpret_cast<const floatx4*>(zbase) + (long long)state[2] * nv : nullptr;
+    const uint64_t offset = MEMBERS ? (1ull + (uint64_t)(unsigned)state[1]) * (uint64_t)nv : offset_base + (uint64_t)(unsigned)state[1] * nper;
+    const uint64_t m = MEMBERS ? members[blockIdx.y] : 0;
+    const long long v0 = MEMBERS ? (long long)blockIdx.y * nv : 0;                // the row's first group in the image
+    const long long nimg = MEMBERS ? (long long)gridDim.y * nv : nv;              // groups of the whole image: one step of z_base
+    const floatx4* z4 = zbase ? reinterpret_cast<const floatx4*>(zbase) + (long long)state[2] * nimg : nullptr;
     floatx4* x4p = reinterpret_cast<floatx4*>(x);
     const floatx4* c4 = reinterpret_cast<const floatx4*>(cond);
     const floatx4* r4 = reinterpret_cast<const floatx4*>(rt_);
@@ -647,7 +654,8 @@ __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const f
     floatx4* rp4 = reinterpret_cast<floatx4*>(rp);
     floatx4* ep4 = reinterpret_cast<floatx4*>(ep);
     const int H = g.H, W = g.W4 * 4;
-    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < nv; v += (long long)gridDim.x * blockDim.x) {
+    for (long long vl = blockIdx.x * (long long)blockDim.x + threadIdx.x; vl < nv; vl += (long long)gridDim.x * blockDim.x) {
+        const long long v = v0 + vl;
         const long long row = v / g.W4;
         const int xg = (int)(v - row * g.W4);
         const long long bc = row / H;
@@ -685,7 +693,7 @@ __global__ __launch_bounds__(256) void drift_step_tiled_kernel(float* x, const f
         floatx4 rt = rv, et = ev;
         if (k.hist_d) rt = extrapolate(rv, rp4[v], k.rho_d);
         if (k.hist_s) et = extrapolate(ev, ep4[v], k.rho_s);
-        const floatx4 zv = step_noise(k.c, z4 != nullptr, [&] { return z4[v]; }, offset + (uint64_t)v, seed);
+        const floatx4 zv = step_noise(k.c, z4 != nullptr, [&] { return z4[v]; }, offset + (uint64_t)vl, seed, m);
         const floatx4 cv = c4[v];
         floatx4 o, oa;
         step_update(xv, rt, et, zv, cv, k.a, k.b, k.c, o, oa);
@@ -936,9 +944,9 @@ extern "C" int idiff_drift_reverse_step_tiled_dev(float* x, const float* r_tiles
     IDIFF_CHECK_ARG(coef_rows == 3 || history_distinct(r_prev, e_prev, {r_tiles, e_tiles, x, x_tiles, xa_tiles}),
                     "drift_reverse_step_tiled_dev: the history buffers must be distinct from each other and from every other operand");
     const long long nv = (long long)B * C * H * (W / 4);
-    hipLaunchKernelGGL(coef_rows == 3 ? drift_step_tiled_kernel<false> : drift_step_tiled_kernel<true>, dim3(stream_grid(nv)), dim3(256), 0,
-                       (hipStream_t)stream, x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1, state, seed,
-                       nper, offset_base);
+    hipLaunchKernelGGL((coef_rows == 3 ? drift_step_tiled_kernel<false, false> : drift_step_tiled_kernel<true, false>), dim3(stream_grid(nv)),
+                       dim3(256), 0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, nv, g, coef, Tp1,
+                       state, seed, nper, offset_base, (const uint64_t*)nullptr);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_tiled_dev");
     return IDIFF_OK;
 }
@@ -1010,6 +1018,33 @@ extern "C" int idiff_drift_reverse_step_members_dev(float* x, const float* r_hat
     hipLaunchKernelGGL(coef_rows == 3 ? drift_step_members_kernel<false> : drift_step_members_kernel<true>, rows_grid(Q, R), dim3(256), 0,
                        (hipStream_t)stream, x, r_hat, e_hat, r_prev, e_prev, z_base, cond, xa, Q, coef, Tp1, state, members_dev, seed);
     IDIFF_CHECK_LAUNCH("drift_reverse_step_members_dev");
+    return IDIFF_OK;
+}
+
+extern "C" int idiff_drift_reverse_step_tiled_members_dev(float* x, const float* r_tiles, const float* e_tiles, float* r_prev, float* e_prev,
+                                                          const float* z_base, const float* cond, float* x_tiles, float* xa_tiles, int R, int C,
+                                                          int H, int W, int ny, int nx, int Ph, int Pw, const int32_t* ytab, const float* ywt,
+                                                          const int32_t* xtab, const float* xwt, const float* coef, int coef_rows, int Tp1,
+                                                          const int32_t* state, const uint64_t* members_dev, uint64_t seed,
+                                                          idiff_stream_t stream) {
+    TileGeom g;
+    IDIFF_CHECK_ARG(x && r_tiles && e_tiles && cond && x_tiles && xa_tiles && coef && state && members_dev && Tp1 > 1 && R > 0 && R <= 65535 &&
+                        tile_geom(g, R, C, H, W, ny, nx, Ph, Pw, ytab, ywt, xtab, xwt),
+                    "drift_reverse_step_tiled_members_dev: bad args (0 < R <= 65535; W, Pw multiples of 4; windows inside and covering the image)");
+    IDIFF_CHECK_ARG(coef_rows == 3 || coef_rows == 5, "drift_reverse_step_tiled_members_dev: coef_rows must be 3 or 5, got %d", coef_rows);
+    IDIFF_CHECK_ARG(aligned16({x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, xwt}),
+                    "drift_reverse_step_tiled_members_dev: operands must be 16-byte aligned");
+    IDIFF_CHECK_ARG(x_tiles != xa_tiles && x_tiles != r_tiles && x_tiles != e_tiles && xa_tiles != r_tiles && xa_tiles != e_tiles &&
+                        x != x_tiles && x != xa_tiles && x != r_tiles && x != e_tiles && x != cond,
+                    "drift_reverse_step_tiled_members_dev: the image and the four window buffers must be distinct");
+    if (const int rc = check_coef_rows("drift_reverse_step_tiled_members_dev", coef_rows, r_prev, e_prev)) return rc;
+    IDIFF_CHECK_ARG(coef_rows == 3 || history_distinct(r_prev, e_prev, {r_tiles, e_tiles, x, x_tiles, xa_tiles}),
+                    "drift_reverse_step_tiled_members_dev: the history buffers must be distinct from each other and from every other operand");
+    const long long Q = (long long)C * H * (W / 4);
+    hipLaunchKernelGGL((coef_rows == 3 ? drift_step_tiled_kernel<false, true> : drift_step_tiled_kernel<true, true>), rows_grid(Q, R), dim3(256),
+                       0, (hipStream_t)stream, x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, Q, g, coef, Tp1, state, seed,
+                       (uint64_t)0, (uint64_t)0, members_dev);
+    IDIFF_CHECK_LAUNCH("drift_reverse_step_tiled_members_dev");
     return IDIFF_OK;
 }
 

@@ -30,6 +30,10 @@ overlapping windows.  The state stays ONE full-resolution image: every step blen
 eps_hat, updates and draws the noise once per pixel on the full image (the plain chain's Philox counters, whatever the tiling), and cuts the
 next step's window inputs out again -- one fused kernel per step beside the nets.
 
+Ensembles of tiled chains (`tiled_ensemble: true`): off, num_samples > 1 and a tiling refuse each other.  On,
+reverse_ddpm_ensemble runs an image larger than the window as tiled member chains: full-resolution member rows, grouped into chains of at
+most max_chain_rows window rows, one fused kernel per step that blends, draws each row's z from its member's stream and scatters.
+
 Credible intervals (`interval: L`): with it reverse_ddpm_ensemble also selects, per pixel, the order statistics of the S
 members that bracket the central level-L interval and the median (one launch, values selected and never rounded) into
 self.last_order_stats.  order_stat_indices states which order statistics those are and the coverage they nominally give.
@@ -191,6 +195,31 @@ def _max_batch(rows):
     if not _is_int(rows) or rows < 1:
         raise ValueError(f"driftSDE: max_batch must be an int >= 1, got {rows!r}")
     return int(rows)
+
+
+def _max_chain_rows(rows):
+    """window rows per chain of a tiled ensemble as an int >= 1; bools, floats and strings are refused like max_batch's"""
+    if not _is_int(rows) or rows < 1:
+        raise ValueError(f"driftSDE: max_chain_rows must be an int >= 1, got {rows!r}")
+    return int(rows)
+
+
+def _tiled_ensemble(flag):
+    """the tiled_ensemble option as a bool (None: False); anything but a bool is refused, like reuse_graph's"""
+    if flag is None:
+        return False
+    if not isinstance(flag, bool):
+        raise ValueError(f"driftSDE: tiled_ensemble must be true or false (or None: false), got {flag!r}")
+    return flag
+
+
+def chain_groups(R, nwin, max_chain_rows):
+    """The chains of a tiled ensemble: its R full-resolution rows, each nwin window rows in the nets, in order, as [(r0, r1), ...] with
+    G = max(1, max_chain_rows // nwin) consecutive rows per chain (the last may hold fewer).  The groups cover 0..R once."""
+    if not (_is_int(R) and R >= 1 and _is_int(nwin) and nwin >= 1):
+        raise ValueError(f"chain_groups: R and nwin must be ints >= 1, got {R!r}, {nwin!r}")
+    G = max(1, _max_chain_rows(max_chain_rows) // nwin)
+    return [(r0, min(r0 + G, R)) for r0 in range(0, R, G)]
 
 
 def _tile_size(tile):
@@ -382,7 +411,7 @@ def session_key(sde, kind, rows, chw, ctx_shape, sched, order, T_stop, text_enco
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
                  sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, tile=None, tile_overlap=None,
-                 interval=None, reuse_graph=None, **_ignored):
+                 interval=None, reuse_graph=None, tiled_ensemble=None, max_chain_rows=128, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -405,8 +434,10 @@ class driftSDE:
         self._jump = None  # ((timesteps, eta, order), coef, next_t) of the last schedule whose tables were built
         self.solver_order = _solver_order(solver_order)
         self.set_sample_steps(sample_T, sample_timesteps)
+        self.tiled_ensemble = _tiled_ensemble(tiled_ensemble)  # read before num_samples and tile: it decides whether the two may meet
         self.num_samples = _num_samples(num_samples)
         self.max_batch = _max_batch(max_batch)
+        self.max_chain_rows = _max_chain_rows(max_chain_rows)
         self._member_base = 1  # next unassigned member id; 0 is the stream of _randn_like and the plain chain
         self.last_members = None
         self._tile = self._tile_o = None
@@ -444,19 +475,30 @@ class driftSDE:
         reverse_ddpm_ensemble reads it; with num_samples = 1 the plain chain runs and it does nothing."""
         self.interval = _interval(level)
 
-    def set_num_samples(self, num_samples=None, max_batch=None):
-        """S members per input for reverse_ddpm_ensemble (None / 1: off -- model.test() then runs reverse_ddpm); max_batch: rows per chain"""
+    def set_num_samples(self, num_samples=None, max_batch=None, max_chain_rows=None):
+        """S members per input for reverse_ddpm_ensemble (None / 1: off -- model.test() then runs reverse_ddpm); max_batch: rows per chain;
+        max_chain_rows: window rows per chain of a tiled ensemble (chain_groups)"""
         num = _num_samples(num_samples)
         self._refuse_ensemble_of_tiles(num, getattr(self, "_tile", None))
         self.num_samples = num
         if max_batch is not None:
             self.max_batch = _max_batch(max_batch)
+        if max_chain_rows is not None:
+            self.max_chain_rows = _max_chain_rows(max_chain_rows)
 
-    @staticmethod
-    def _refuse_ensemble_of_tiles(num_samples, tile):
-        if num_samples > 1 and tile is not None:
+    def set_tiled_ensemble(self, flag=None):
+        """True: num_samples > 1 and a tiling may be set together, and reverse_ddpm_ensemble runs an image that exceeds the window as
+        tiled member chains.  False / None: the two options refuse each other; refused while both are set."""
+        flag = _tiled_ensemble(flag)
+        if not flag and self.num_samples > 1 and self._tile is not None:
+            raise ValueError(f"driftSDE: tiled_ensemble cannot be turned off while num_samples = {self.num_samples} and tile = "
+                             f"{list(self._tile)} are both set; unset one of the two first")
+        self.tiled_ensemble = flag
+
+    def _refuse_ensemble_of_tiles(self, num_samples, tile):
+        if num_samples > 1 and tile is not None and not self.tiled_ensemble:
             raise ValueError(f"driftSDE: num_samples = {num_samples} together with tile = {list(tile)} is not supported: a posterior ensemble "
-                             "of a tiled chain is out of scope; unset one of the two")
+                             "of a tiled chain is out of scope; unset one of the two, or set tiled_ensemble: true")
 
     def set_tiling(self, tile=None, overlap=None):
         """Tiled sampling: windows of `tile` = P or [Ph, Pw] pixels (multiples of 4) that overlap by `overlap` (a multiple of 4 in
@@ -734,12 +776,15 @@ class driftSDE:
         row.  A step runs predict on chunks of at most sde.max_batch window rows, lands the chunks' predictions in the persistent r_tiles /
         e_tiles (one chunk: the nets' outputs are used as they are), then the fused tiled step on the full image -- which also rewrites
         the window inputs x_tiles / xa_tiles -- and the state advance over all window rows.  Warm step, capture, replay and the Philox
-        accounting (nper = the FULL image's float4 count, as the plain chain's) are Stepper's."""
+        accounting (nper = the FULL image's float4 count, as the plain chain's) are Stepper's.
+        `members` (int64 [rows of x] on the device) makes x the full-resolution rows of an ensemble: row r draws its z from member
+        members[r]'s stream as in the untiled member chain, whatever the tiling, and the sde's stream is left alone; `xa` hands in the
+        full-resolution x - cond (ops.ensemble_init)."""
 
         def __init__(self, sde, x, cond, plan, names, text_encoder, image_context, **kw):
             super().__init__(sde, x, cond, names, text_encoder, image_context, **kw)
-            if self.members is not None:
-                raise ValueError("TiledStepper: member streams are not supported")
+            if self.members is not None and (self.members.dim() != 1 or self.members.numel() != x.shape[0]):
+                raise ValueError(f"TiledStepper: members must hold one id per full-resolution row ({x.shape[0]})")
             self.plan = plan
             R = x.shape[0] * plan.ny * plan.nx
             if len(names) != R or (image_context is not None and image_context.shape[0] != R):
@@ -767,6 +812,10 @@ class driftSDE:
             return self.r_tiles, self.e_tiles
 
         def _update(self, r_tiles, e_tiles):
+            if self.members is not None:
+                ops.drift_reverse_step_tiled_members_dev(self.x, r_tiles, e_tiles, self.r_prev, self.e_prev, self.noises, self.cond, self.x_tiles,
+                                                         self.xa_tiles, self.plan, self.coef, self.state, self.members, self.sde.seed)
+                return
             ops.drift_reverse_step_tiled_dev(self.x, r_tiles, e_tiles, self.r_prev, self.e_prev, self.noises, self.cond, self.x_tiles,
                                              self.xa_tiles, self.plan, self.coef, self.state, self.sde.seed, self.nper, self.off_base)
 
@@ -998,13 +1047,23 @@ class driftSDE:
         ([steps, B*S, ...]) injects the per-step draws.  self.last_members: the ids used, [B, S].
         With `interval` = L set, self.last_order_stats = dict(lo, hi, median [B, ...], level, nominal, ks): the order statistics of
         order_stat_indices(S, L) as contiguous maps, from one ops.ensemble_order_stats launch over the samples (plus one axpby for the
-        median of an even S, and for B > 1 one ops.gather_channel per map); None without it."""
+        median of an even S, and for B > 1 one ops.gather_channel per map); None without it.
+        With `tiled_ensemble` on and a tiling set, an image that exceeds the window in some axis (reverse_ddpm's rule; W a multiple of 4)
+        runs as tiled member chains: the rows start at full resolution (ops.ensemble_init), are grouped in order by chain_groups(B*S,
+        ny*nx, max_chain_rows), and each group is one TiledStepper over its rows.  A member's noise is the untiled chain's, so neither
+        the tiling nor the grouping changes which z a pixel gets.  self.last_tiles: the grid (None on the untiled path); reuse_graph
+        does not apply (a tiled chain captures per call)."""
         S = self.num_samples if num_samples is None else _num_samples(num_samples)
         self._refuse_ensemble_of_tiles(S, self._tile)
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_ensemble")
         cond = cond.contiguous()
         B = cond.shape[0]
         R = B * S
+        # reverse_ddpm's rule: with the switch on, an image that exceeds the window in some axis runs as tiled member chains
+        tiled = (self.tiled_ensemble and self._tile is not None and cond.dim() == 4
+                 and (cond.shape[2] > self._tile[0] or cond.shape[3] > self._tile[1]))
+        if tiled and cond.shape[3] % 4:
+            raise ValueError(f"reverse_ddpm_ensemble: the image width {cond.shape[3]} is not a multiple of 4")
         if (cond.numel() // B) % 4:
             raise ValueError(f"reverse_ddpm_ensemble: a sample has {cond.numel() // B} elements, not a multiple of 4")
         if noises is not None and (noises.dim() < 2 or noises.shape[1] != R):
@@ -1014,8 +1073,22 @@ class driftSDE:
         names_rep = [n for n in names for _ in range(S)]
         ctx_rep = None if image_context is None else image_context.repeat_interleave(S, dim=0)
         self.last_session = None
-        idx = self._session_indices(names_rep, cond, image_context, nsteps) if noises is None else None
-        if idx is not None:
+        self.last_tiles = None
+        idx = self._session_indices(names_rep, cond, image_context, nsteps) if (noises is None and not tiled) else None
+        if tiled:
+            # chains of G consecutive full-resolution rows, each one TiledStepper over its G*nwin window rows; a tiled chain always
+            # captures per call
+            plan = self._tile_plan(cond.shape[2], cond.shape[3], cond.device)
+            nwin = plan.ny * plan.nx
+            cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
+            for r0, r1 in chain_groups(R, nwin, self.max_chain_rows):
+                stepper = driftSDE.TiledStepper(self, x[r0:r1], cond_rep[r0:r1], plan, [n for n in names_rep[r0:r1] for _ in range(nwin)],
+                                                text_encoder, None if ctx_rep is None else ctx_rep[r0:r1].repeat_interleave(nwin, dim=0),
+                                                noises=None if noises is None else noises[:, r0:r1].contiguous(), t_stop=T_stop,
+                                                timesteps=sched, solver_order=order, members=mdev[r0:r1], xa=xa[r0:r1])
+                stepper.run(nsteps)
+            self.last_tiles = plan.grid
+        elif idx is not None:
             # each chunk through the member session of its row count: a full chunk and a shorter last chunk are two sessions
             x = torch.empty((R,) + tuple(cond.shape[1:]), dtype=torch.float32, device=cond.device)
             how = []

@@ -1015,6 +1015,33 @@ def drift_reverse_step_tiled_dev(x, r_tiles, e_tiles, r_prev, e_prev, z_base, co
           "drift_reverse_step_tiled_dev")
 
 
+def drift_reverse_step_tiled_members_dev(x, r_tiles, e_tiles, r_prev, e_prev, z_base, cond, x_tiles, xa_tiles, plan, coef, state, members,
+                                         seed):
+    """drift_reverse_step_tiled_dev on the rows of an ensemble: x [R, C, H, W] holds one member of one image per row, the window
+    buffers [R*ny*nx, C, Ph, Pw], and row r's z comes from member members[r]'s stream (int64 [R] on the device) at draw 1 + state[1],
+    as in drift_reverse_step_members_dev, or from z_base [steps, R, C, H, W]"""
+    lib = _lib.load()
+    _c(x, "x"), _c(r_tiles, "r_tiles"), _c(e_tiles, "e_tiles"), _c(r_prev, "r_prev"), _c(e_prev, "e_prev"), _c(z_base, "z"), _c(cond, "cond")
+    _c(x_tiles, "x_tiles"), _c(xa_tiles, "xa_tiles"), _c(coef, "coef"), _c(state, "state", torch.int32)
+    dims = _tile_args(plan, x, "drift_reverse_step_tiled_members_dev")
+    R = dims[0]
+    nt = R * plan.ny * plan.nx * dims[1] * plan.Ph * plan.Pw
+    _step_tables(coef, (3, 5), state)
+    for t in (r_tiles, e_tiles, x_tiles, xa_tiles):
+        if t.numel() != nt:
+            raise _lib.IdiffError(f"drift_reverse_step_tiled_members_dev: a window buffer holds {t.numel()} elements, the plan needs {nt}")
+    for t in (r_prev, e_prev, cond):
+        assert t is None or t.numel() == x.numel()
+    assert z_base is None or (z_base.numel() % x.numel() == 0 and z_base.numel() >= x.numel())
+    if members is None:
+        raise _lib.IdiffError("drift_reverse_step_tiled_members_dev: members is required (int64 [R] on the device, from member_ids())")
+    check(lib.idiff_drift_reverse_step_tiled_members_dev(_p(x), _p(r_tiles), _p(e_tiles), _p(r_prev), _p(e_prev), _p(z_base), _p(cond),
+                                                         _p(x_tiles), _p(xa_tiles), *dims, C.c_void_p(plan.ytab.data_ptr()), _p(plan.ywt),
+                                                         C.c_void_p(plan.xtab.data_ptr()), _p(plan.xwt), _p(coef), coef.shape[0],
+                                                         coef.shape[1], C.c_void_p(state.data_ptr()), _members(members, R), seed, _stream()),
+          "drift_reverse_step_tiled_members_dev")
+
+
 def step_state_advance(state, tdev, T, t_stop=0):
     lib = _lib.load()
     _c(tdev, "tdev")

@@ -13,7 +13,7 @@ With `--scores` on top of `--num-samples S` the ensemble is verified against the
 `RANK_DEV` (the rank histogram's distance from flat) are listed per image, a `<i>_crps_WxHx1.raw` map is written, and per artifact type the
 pooled scores are printed and the pooled rank histogram goes to `rank_hist.json`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
-full-resolution chain.  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
+full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
@@ -57,6 +57,11 @@ def main(argv=None):
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
                         help="driftSDE tile_overlap: pixels shared by adjacent windows (default tile // 8; overrides the YAML)")
+    parser.add_argument("--tiled-ensemble", action="store_true",
+                        help="driftSDE tiled_ensemble: let --num-samples and --tile meet: an image larger than the window is restored as an "
+                             "ensemble of tiled chains (without it the two options refuse each other; overrides the YAML)")
+    parser.add_argument("--max-chain-rows", type=int, default=None, metavar="N",
+                        help="driftSDE max_chain_rows: window rows per chain of a tiled ensemble (default 128; overrides the YAML)")
     parser.add_argument("--reuse-graph", action="store_true",
                         help="driftSDE reuse_graph: keep the captured step graph and replay it for every later image of the same shape "
                              "(same bits; overrides the YAML)")
@@ -89,6 +94,10 @@ def main(argv=None):
         sde_opt['tile'] = args.tile[0] if len(args.tile) == 1 else list(args.tile)
     if args.tile_overlap is not None:
         sde_opt['tile_overlap'] = args.tile_overlap
+    if args.tiled_ensemble:
+        sde_opt['tiled_ensemble'] = True
+    if args.max_chain_rows is not None:
+        sde_opt['max_chain_rows'] = args.max_chain_rows
     if args.reuse_graph:
         sde_opt['reuse_graph'] = True
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
