@@ -688,7 +688,8 @@ def test_conv_groupnorm_finalize_riding_on_the_conv_call_equals_separate_launch(
 # ---- 1x1 conv on the bf16 matrix cores, fp32 operands split three ways (csrc/conv1x1_x3.hip) ------------------------------------------
 @pytest.mark.parametrize("B,C0,C1,Cout,H,W,variant", [
     (2, 64, 64, 64, 32, 32, "res"),        # the level-0 residual 1x1 (virtual concat), 4 chunks of 32
-    (1, 64, 80, 64, 64, 64, "plain"),      # Cin = 144: last chunk half empty; the sources meet inside a chunk (octet boundary)
+    (1, 64, 80, 64, 64, 64, "plain"),      # Cin = 144: last chunk half empty; the sources meet at channel 64, a chunk boundary (chunks of
+                                           # 32) -- as 128 + 80 below does: a boundary inside a chunk is a row of test_mfma_fwd_gpu.py
     (2, 128, 80, 128, 16, 32, "vec_aux"),  # 208 -> 128, two channel blocks, per-(b,c) vector and the "+ silu(a*aux+b)" term
     (1, 256, 0, 768, 32, 32, "plain"),     # single source (the mid-attention qkv projection), 12 channel blocks
     (3, 32, 0, 64, 8, 32, "res"),          # one chunk, 256 pixels per sample: one tile
