@@ -1277,18 +1277,10 @@ static int smm_xattn_bwd_impl(const float* qf, const float* mem, const float* o,
     hipStream_t st = (hipStream_t)stream;
     const int xcb = (Cm / 4 + 31) / 32;
     const size_t lds = (size_t)(4 * xcb * 32 * 33 + 2 * 32 * (Cm + 1) + 4 * 2304 + 64) * sizeof(float);
-    static bool attr[2] = {false, false};
-    const int which = Cm == 256 ? 0 : 1;
-    if (!attr[which]) {
-        hipError_t e = Cm == 256 ? hipFuncSetAttribute(reinterpret_cast<const void*>(smm_xattn_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                 : hipFuncSetAttribute(reinterpret_cast<const void*>(smm_xattn_bwd_kernel<18>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "smm_xattn_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr[which] = true;
-    }
-    if (Cm == 256)
-        hipLaunchKernelGGL(smm_xattn_bwd_kernel<64>, dim3(ns, B), dim3(256), lds, st, qf, mem, o, lse, d_o, ws, dmem, rows, N, ns, kps, scale, accumulate);
-    else
-        hipLaunchKernelGGL(smm_xattn_bwd_kernel<18>, dim3(ns, B), dim3(256), lds, st, qf, mem, o, lse, d_o, ws, dmem, rows, N, ns, kps, scale, accumulate);
+    static idiff_dyn_lds_cache attr[2];
+    auto kern = Cm == 256 ? smm_xattn_bwd_kernel<64> : smm_xattn_bwd_kernel<18>;
+    if (const int rc = idiff_dyn_lds(attr[Cm == 256 ? 0 : 1], kern, lds, "smm_xattn_bwd")) return rc;
+    hipLaunchKernelGGL(kern, dim3(ns, B), dim3(256), lds, st, qf, mem, o, lse, d_o, ws, dmem, rows, N, ns, kps, scale, accumulate);
     IDIFF_CHECK_LAUNCH("smm_xattn_bwd");
     hipLaunchKernelGGL(smm_xattn_bwd_combine_kernel, dim3((Cm * 32 + 255) / 256, B), dim3(256), 0, st, ws, dqf, rows, ns, Cm);
     IDIFF_CHECK_LAUNCH("smm_xattn_bwd_combine");

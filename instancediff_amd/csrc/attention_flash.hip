@@ -222,12 +222,8 @@ extern "C" int idiff_smm_xattn_kv_f16_fwd(const float* q, const float* k, const 
     int ns, kps;
     fx_split(N, &ns, &kps);
     const size_t lds = (size_t)4 * 2 * FX_TILE * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smm_xattn_kv_f16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "smm_xattn_kv_f16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = true;
-    }
+    static idiff_dyn_lds_cache attr;
+    if (const int rc = idiff_dyn_lds(attr, smm_xattn_kv_f16_kernel, lds, "smm_xattn_kv_f16")) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(smm_xattn_kv_f16_kernel, dim3(ns, B), dim3(256), lds, st, q, k, v, ws, Nq, N, ns, kps, scale);
     IDIFF_CHECK_LAUNCH("smm_xattn_kv_f16_fwd");

@@ -885,8 +885,7 @@ extern "C" int idiff_chan_layernorm_bwd(const float* dy, int64_t dy_bstride, con
         const size_t lds = (size_t)(512 + 4 * jmax + 4 * jmax * 65) * sizeof(float);
         static idiff_dyn_lds_cache lc[2];
         auto kern = C <= 128 ? chan_ln_bwd_fused_kernel<32> : chan_ln_bwd_fused_kernel<64>;
-        hipError_t e = idiff_ensure_dyn_lds(lc[C <= 128 ? 0 : 1], reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "chan_layernorm_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        if (const int rc = idiff_dyn_lds(lc[C <= 128 ? 0 : 1], kern, lds, "chan_layernorm_bwd")) return rc;
         hipLaunchKernelGGL(kern, dim3(G, B), dim3(256), lds, ST, dy, (long long)dy_bstride, x, (long long)x_bstride, gamma, mean_rstd, dx,
                            (long long)dx_bstride, ws, C, HW, tpw);
         IDIFF_CHECK_LAUNCH("chan_layernorm_bwd_fused");

@@ -48,6 +48,15 @@ inline hipError_t idiff_ensure_dyn_lds(idiff_dyn_lds_cache& c, const void* fn, s
     }
     return hipSuccess;
 }
+// The preamble of every launch with more than the default dynamic LDS: `bytes` must fit the 160 KB of a CU, and the kernel's limit is
+// raised to it.  `call` names the entry point in the message.
+template <typename K>
+inline int idiff_dyn_lds(idiff_dyn_lds_cache& c, K kern, size_t bytes, const char* call) {
+    if (bytes > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "%s: LDS budget exceeded (%zu bytes)", call, bytes);
+    const hipError_t e = idiff_ensure_dyn_lds(c, reinterpret_cast<const void*>(kern), bytes);
+    if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "%s: hipFuncSetAttribute: %s", call, hipGetErrorString(e));
+    return IDIFF_OK;
+}
 
 // Compute units of the current device (the persistent kernels' grid), cached per device like the attribute above.  False: the query failed.
 inline bool idiff_num_cu(int* n) {

@@ -4,6 +4,26 @@
 
 namespace idiff_detail {
 
+// The virtual problem a descriptor's mode makes of its sources: unshuffle reads 4 x C0 channels at half the size, upsample writes
+// twice the size, two sources are one concatenated input.
+struct ConvShape {
+    int C0v, C1v, Cin, Hout, Wout;
+};
+// Derives it for the forward, the weight gradient and the workspace query alike.  Returns the rule of its mode that the descriptor
+// breaks, or null; the shape is filled in either way (the workspace query answers without judging).  The rules that only say which
+// instantiations the direct kernels have (upsample needs ks=3, ks=7 needs normal mode) stay where such a kernel is chosen.
+inline const char* conv_shape(const idiff_conv_desc* d, ConvShape* s) {
+    const bool unsh = d->mode == IDIFF_CONV_UNSHUFFLE2, ups = d->mode == IDIFF_CONV_UPSAMPLE2;
+    s->C0v = unsh ? d->C0 * 4 : d->C0;
+    s->C1v = d->C1;  // none under unshuffle (below)
+    s->Cin = s->C0v + s->C1v;
+    s->Hout = ups ? d->Hin * 2 : (unsh ? d->Hin / 2 : d->Hin);
+    s->Wout = ups ? d->Win * 2 : (unsh ? d->Win / 2 : d->Win);
+    if (unsh && !(d->ks == 1 && d->C1 == 0)) return "unshuffle mode needs ks=1 and a single source";
+    if (unsh && !(d->Hin % 2 == 0 && d->Win % 2 == 0)) return "unshuffle needs even H, W";
+    return nullptr;
+}
+
 // arguments of the GroupNorm finalize that rides on a conv call (idiff_conv_desc.gn_*; the finalize is a launch behind the conv)
 struct GnTail {
     const float* gamma;

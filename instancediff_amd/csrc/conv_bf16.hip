@@ -266,8 +266,7 @@ int launch_conv_bf16(const ConvArgs& a, int mode, const void* wbf16, hipStream_t
     const size_t lds = FIXED_LDS + (a.pro_a ? (size_t)2 * a.C0r * sizeof(float) : 0);
     static idiff_dyn_lds_cache lds_cache[2];
     auto kern = mode == IDIFF_CONV_UPSAMPLE2 ? conv_bf16_kernel<IDIFF_CONV_UPSAMPLE2> : conv_bf16_kernel<IDIFF_CONV_NORMAL>;
-    hipError_t e = idiff_ensure_dyn_lds(lds_cache[mode == IDIFF_CONV_UPSAMPLE2], reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(bf16): hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (const int rc = idiff_dyn_lds(lds_cache[mode == IDIFF_CONV_UPSAMPLE2], kern, lds, "conv2d(bf16)")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.total_wg), dim3(256), lds, st, a, static_cast<const uintx4*>(wbf16));
     IDIFF_CHECK_LAUNCH("conv2d_fwd(bf16)");
     return IDIFF_OK;

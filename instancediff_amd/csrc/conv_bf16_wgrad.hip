@@ -188,8 +188,7 @@ int launch_bf16_wgrad(const WwArgs& a, float* dw, int accumulate, hipStream_t st
     static idiff_dyn_lds_cache lds_cache[2];
     const bool ups = a.ups != 0;
     auto kern = ups ? wgrad_bf16_kernel<IDIFF_CONV_UPSAMPLE2> : wgrad_bf16_kernel<IDIFF_CONV_NORMAL>;
-    hipError_t e = idiff_ensure_dyn_lds(lds_cache[ups], reinterpret_cast<const void*>(kern), lds);
-    if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad(bf16): hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (const int rc = idiff_dyn_lds(lds_cache[ups], kern, lds, "conv2d_wgrad(bf16)")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds, st, a, g);
     IDIFF_CHECK_LAUNCH("conv2d_wgrad(bf16)");
     const long long n = 9ll * a.Cin * a.Cout;

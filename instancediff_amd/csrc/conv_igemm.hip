@@ -519,13 +519,9 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
     size_t taboff = (size_t)2 * (IN_TILE + W_TILE);
     if (KS == 1 && TWL == 8 && MODE == IDIFF_CONV_NORMAL && (size_t)32 * 260 > taboff) taboff = (size_t)32 * 260;  // = TABOFF of the kernel
     const size_t lds = (taboff + (a.pro_a ? 2 * (size_t)a.C0r : 0) + 4 * BM) * sizeof(float);
-    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "conv2d: LDS budget exceeded (%zu bytes)", lds);
     static idiff_dyn_lds_cache lds_cache;
     auto kern = conv_igemm_kernel<KS, CK, TWL, MODE, VECW, MB, SPEC>;
-    {
-        hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.total_wg), dim3(256), lds, st, a);
     IDIFF_CHECK_LAUNCH("conv2d_fwd");
     return IDIFF_OK;
@@ -593,8 +589,16 @@ extern "C" int idiff_conv2d_num_tiles(int Hout, int Wout) {
     return ((Wout + TW - 1) / TW) * ((Hout + TH - 1) / TH);
 }
 
-// plan = true: everything up to the choice of the kernel (argument checks, the per-sample-shape rules, g_last_algo), no launch
-static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const bool plan) {
+// A forward call in three steps: conv2d_args (descriptor -> ConvArgs and the direct kernel's tiling, with the argument checks),
+// conv2d_choose (the kernel, by the per-sample-shape rules) and conv2d_launch.  idiff_conv2d_plan is the first two.
+struct ConvPlan {
+    int algo;        // IDIFF_CONV_ALGO_*
+    ConvArgs a;      // what the chosen kernel takes
+    int twl, mb;     // the direct kernel's tile
+    bool vecw;
+};
+
+static int conv2d_args(const idiff_conv_desc* d, ConvPlan* p) {
     IDIFF_CHECK_ARG(d && d->src0 && d->wpk && d->out, "conv2d: null pointer");
     IDIFF_CHECK_ARG(d->B > 0 && d->C0 > 0 && d->Cout > 0 && d->Hin > 0 && d->Win > 0, "conv2d: bad dims");
     IDIFF_CHECK_ARG(d->ks == 1 || d->ks == 3 || d->ks == 7, "conv2d: ks must be 1, 3 or 7 (got %d)", d->ks);
@@ -603,7 +607,7 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
     IDIFF_CHECK_ARG(!(d->pro_a && d->C1 > 0), "conv2d: prologue needs a single source");
     IDIFF_CHECK_ARG((d->pro_a == nullptr) == (d->pro_b == nullptr), "conv2d: pro_a/pro_b must both be set");
     IDIFF_CHECK_ARG(!d->aux || (d->aux_a && d->aux_b), "conv2d: aux needs aux_a/aux_b");
-    ConvArgs a;
+    ConvArgs& a = p->a;
     a.src0 = d->src0;
     a.src1 = d->src1;
     a.bs0 = d->src0_bstride;
@@ -630,44 +634,21 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
     a.aux_b = d->aux_b;
     a.stats = d->stats;
     memset(&a.gn, 0, sizeof(a.gn));
-    const bool want_gn = d->gn_out_a != nullptr;
-    if (want_gn) {
+    if (d->gn_out_a) {
         IDIFF_CHECK_ARG(d->stats && d->gn_out_b && d->gn_groups > 0 && d->Cout % d->gn_groups == 0 && d->Cout / d->gn_groups <= 256,
                         "conv2d: GroupNorm finalize needs stats, gn_out_b and groups dividing Cout (<= 256 channels per group)");
         a.gn.gamma = d->gn_gamma, a.gn.beta = d->gn_beta, a.gn.film = d->gn_film, a.gn.film_ld = d->gn_film_ld, a.gn.eps = d->gn_eps;
         a.gn.groups = d->gn_groups, a.gn.out_a = d->gn_out_a, a.gn.out_b = d->gn_out_b, a.gn.mean_rstd = d->gn_mean_rstd;
     }
-    // the separate finalize launch behind kernels without the fused tail
-    auto finalize_after = [&](int rc) -> int {
-        if (rc != IDIFF_OK || !want_gn) return rc;
-        return idiff_gn_finalize(d->stats, a.ntiles, a.B, a.Cout, d->gn_groups, a.Hout * a.Wout, d->gn_gamma, d->gn_beta, d->gn_film, d->gn_film_ld,
-                                 d->gn_eps, d->gn_out_a, d->gn_out_b, d->gn_mean_rstd, stream);
-    };
-    if (d->mode == IDIFF_CONV_UNSHUFFLE2) {
-        IDIFF_CHECK_ARG(d->ks == 1 && d->C1 == 0, "conv2d: unshuffle mode needs ks=1 and a single source");
-        IDIFF_CHECK_ARG(d->Hin % 2 == 0 && d->Win % 2 == 0, "conv2d: unshuffle needs even H, W");
-        a.C0v = d->C0 * 4;
-        a.C1v = 0;
-        a.Hout = d->Hin / 2;
-        a.Wout = d->Win / 2;
-    } else if (d->mode == IDIFF_CONV_UPSAMPLE2) {
-        a.C0v = d->C0;
-        a.C1v = d->C1;
-        a.Hout = d->Hin * 2;
-        a.Wout = d->Win * 2;
-    } else {
-        a.C0v = d->C0;
-        a.C1v = d->C1;
-        a.Hout = d->Hin;
-        a.Wout = d->Win;
-    }
-    a.Cin = a.C0v + a.C1v;
+    idiff_detail::ConvShape s;
+    if (const char* why = idiff_detail::conv_shape(d, &s)) IDIFF_FAIL(IDIFF_E_BADARG, "conv2d: %s", why);
+    a.C0v = s.C0v, a.C1v = s.C1v, a.Cin = s.Cin, a.Hout = s.Hout, a.Wout = s.Wout;
     IDIFF_CHECK_ARG(a.bs0 >= (long long)d->C0 * d->Hin * d->Win, "conv2d: src0_bstride too small");
     IDIFF_CHECK_ARG(d->C1 == 0 || a.bs1 >= (long long)d->C1 * d->Hin * d->Win, "conv2d: src1_bstride too small");
     IDIFF_CHECK_ARG(a.obs >= (long long)d->Cout * a.Hout * a.Wout, "conv2d: out_bstride too small");
     int twl = pick_twl(a.Wout);
-    const int mb = a.Cout <= 32 ? 1 : 2;
-    const bool vecw = (a.Cout % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.wpk) & 15) == 0);
+    const int mb = p->mb = a.Cout <= 32 ? 1 : 2;
+    const bool vecw = p->vecw = (a.Cout % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.wpk) & 15) == 0);
     // A 1x1 conv has no halo, so its pixel tile may be any 256 pixels: flatten the image to one row and take 256
     // consecutive pixels per tile -- 1 KB contiguous per input channel instead of 8 rows of 128 B (HBM-bound layers).
     // Not when GroupNorm partials are requested: their layout is per 8x32 patch (idiff_conv2d_num_tiles).
@@ -687,7 +668,18 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
     const long long total = (long long)a.B * a.ntiles * a.ncob;
     IDIFF_CHECK_ARG(total < (1ll << 31), "conv2d: grid too large");
     a.total_wg = (unsigned)total;
-    hipStream_t st = (hipStream_t)stream;
+    p->twl = twl;
+    return IDIFF_OK;
+}
+
+// Sets p->algo, and p->a where the chosen kernel tiles the layer its own way.  No HIP call, no state but the error text.
+static int conv2d_choose(const idiff_conv_desc* d, ConvPlan* p) {
+    const ConvArgs& a = p->a;
+    const int twl = p->twl;
+    auto take = [p](int algo) {
+        p->algo = algo;
+        return IDIFF_OK;
+    };
     const bool hard = d->algo_request > 0;
     const int req = (hard ? d->algo_request : -d->algo_request) - 1;  // -1: the library picks
     IDIFF_CHECK_ARG(req == -1 || req == IDIFF_CONV_ALGO_DIRECT || req == IDIFF_CONV_ALGO_WINOGRAD || req == IDIFF_CONV_ALGO_WINOGRAD4 ||
@@ -701,11 +693,7 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
         const bool can = idiff_detail::conv_bf16_eligible(a, d->ks, d->mode, d->wbf16);
         IDIFF_CHECK_ARG(!(hard && reqbf) || can, "conv2d: algo_request bf16 but the layer is not a 3x3 that tiles for it (Cout %% 64, C0 / C1 %% 32, "
                         "Hout %% 8, Wout %% 32) or has no bf16 image");
-        if (can && (reqbf || (req == -1 && d->operands == 1))) {
-            g_last_algo = IDIFF_CONV_ALGO_BF16;
-            if (plan) return IDIFF_OK;
-            return finalize_after(idiff_detail::launch_conv_bf16(a, d->mode, d->wbf16, st));
-        }
+        if (can && (reqbf || (req == -1 && d->operands == 1))) return take(IDIFF_CONV_ALGO_BF16);
     }
     // Flattened 1x1 layers with a split weight image: the bf16x3 kernel (conv1x1_x3.hip) -- fp32-class result at 2.67x the matrix
     // throughput; decided on the layer's shape only.  IDIFF_X3=0 (A/B runs) keeps them on the f32 matrix cores.
@@ -731,9 +719,8 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
         }
         IDIFF_CHECK_ARG(!(hard && reqx3) || can, "conv2d: algo_request bf16x3 but the layer is not a 1x1 that tiles by 256 pixels with a split weight image");
         if (can && (reqx3 || (req == -1 && x3_on))) {
-            g_last_algo = IDIFF_CONV_ALGO_X3;
-            if (plan) return IDIFF_OK;
-            return idiff_detail::launch_conv1x1_x3(ax, d->mode, d->wx3, st);
+            p->a = ax;
+            return take(IDIFF_CONV_ALGO_X3);
         }
     }
     // Which F(4x4,3x3) kernel (both read the same weight image): decided on the layer's PER-SAMPLE shape only.
@@ -757,51 +744,57 @@ static int conv2d_run(const idiff_conv_desc* d, idiff_stream_t stream, const boo
         else if (req4 && w4_ok) half = false;
         else if (items16 >= 16 && w4_ok) half = w4h_mode == 2 || (w4h_mode == 3 && a.src1 != nullptr);
         else half = w4h_mode >= 1 && items8 >= 16;
-        if (half) {
-            g_last_algo = IDIFF_CONV_ALGO_WINOGRAD4H;
-            if (plan) return IDIFF_OK;
-            return finalize_after(idiff_detail::launch_conv_wino4h(a, d->mode, st));
-        }
-        if (w4_ok && (req4 || items16 >= 16)) {
-            g_last_algo = IDIFF_CONV_ALGO_WINOGRAD4;
-            if (plan) return IDIFF_OK;
-            return finalize_after(idiff_detail::launch_conv_wino4(a, d->mode, st));
-        }
+        if (half) return take(IDIFF_CONV_ALGO_WINOGRAD4H);
+        if (w4_ok && (req4 || items16 >= 16)) return take(IDIFF_CONV_ALGO_WINOGRAD4);
     }
     IDIFF_CHECK_ARG(!hard || !(req4 || req4h), "conv2d: algo_request F(4x4,3x3) but the shape does not tile for it");
-    if ((req == -1 || req == IDIFF_CONV_ALGO_WINOGRAD || !hard) && req != IDIFF_CONV_ALGO_DIRECT && idiff_detail::conv_wino_eligible(a, d->ks, d->mode)) {
-        g_last_algo = IDIFF_CONV_ALGO_WINOGRAD;
-        if (plan) return IDIFF_OK;
-        return finalize_after(idiff_detail::launch_conv_wino(a, d->mode, st));
-    }
+    if ((req == -1 || req == IDIFF_CONV_ALGO_WINOGRAD || !hard) && req != IDIFF_CONV_ALGO_DIRECT && idiff_detail::conv_wino_eligible(a, d->ks, d->mode))
+        return take(IDIFF_CONV_ALGO_WINOGRAD);
     IDIFF_CHECK_ARG(!hard || req != IDIFF_CONV_ALGO_WINOGRAD, "conv2d: algo_request F(2x2,3x3) but the shape does not tile for it");
-    g_last_algo = IDIFF_CONV_ALGO_DIRECT;
-    if (plan) {
-        IDIFF_CHECK_ARG(!(d->ks == 1 && d->mode == IDIFF_CONV_UPSAMPLE2), "conv2d: upsample mode needs ks=3");
-        IDIFF_CHECK_ARG(d->ks != 7 || d->mode == IDIFF_CONV_NORMAL, "conv2d: ks=7 needs normal mode");
-        return IDIFF_OK;
-    }
-    if (d->ks == 3) {
-        if (d->mode == IDIFF_CONV_NORMAL) return finalize_after(dispatch_mb<3, 8, IDIFF_CONV_NORMAL>(a, twl, mb, vecw, st));
-        return finalize_after(dispatch_mb<3, 8, IDIFF_CONV_UPSAMPLE2>(a, twl, mb, vecw, st));
-    }
-    if (d->ks == 1) {
-        IDIFF_CHECK_ARG(d->mode != IDIFF_CONV_UPSAMPLE2, "conv2d: upsample mode needs ks=3");
-        if (d->mode == IDIFF_CONV_NORMAL) return finalize_after(dispatch_mb<1, 16, IDIFF_CONV_NORMAL>(a, twl, mb, vecw, st));
-        return finalize_after(dispatch_mb<1, 16, IDIFF_CONV_UNSHUFFLE2>(a, twl, mb, vecw, st));
-    }
-    IDIFF_CHECK_ARG(d->mode == IDIFF_CONV_NORMAL, "conv2d: ks=7 needs normal mode");
-    return finalize_after(dispatch_mb<7, 2, IDIFF_CONV_NORMAL>(a, twl, mb, vecw, st));
+    // the direct kernel: 3x3 normal / upsample, 1x1 normal / unshuffle (conv_shape: never 3x3), 7x7 normal
+    IDIFF_CHECK_ARG(!(d->ks == 1 && d->mode == IDIFF_CONV_UPSAMPLE2), "conv2d: upsample mode needs ks=3");
+    IDIFF_CHECK_ARG(d->ks != 7 || d->mode == IDIFF_CONV_NORMAL, "conv2d: ks=7 needs normal mode");
+    return take(IDIFF_CONV_ALGO_DIRECT);
 }
 
-extern "C" int idiff_conv2d_fwd(const idiff_conv_desc* d, idiff_stream_t stream) { return conv2d_run(d, stream, false); }
+static int conv2d_launch(const idiff_conv_desc* d, const ConvPlan& p, idiff_stream_t stream) {
+    const ConvArgs& a = p.a;
+    hipStream_t st = (hipStream_t)stream;
+    const bool normal = d->mode == IDIFF_CONV_NORMAL;
+    int rc;
+    switch (p.algo) {
+        case IDIFF_CONV_ALGO_X3: return idiff_detail::launch_conv1x1_x3(a, d->mode, d->wx3, st);  // (never with GroupNorm partials)
+        case IDIFF_CONV_ALGO_BF16: rc = idiff_detail::launch_conv_bf16(a, d->mode, d->wbf16, st); break;
+        case IDIFF_CONV_ALGO_WINOGRAD4H: rc = idiff_detail::launch_conv_wino4h(a, d->mode, st); break;
+        case IDIFF_CONV_ALGO_WINOGRAD4: rc = idiff_detail::launch_conv_wino4(a, d->mode, st); break;
+        case IDIFF_CONV_ALGO_WINOGRAD: rc = idiff_detail::launch_conv_wino(a, d->mode, st); break;
+        default:
+            if (d->ks == 3)
+                rc = normal ? dispatch_mb<3, 8, IDIFF_CONV_NORMAL>(a, p.twl, p.mb, p.vecw, st) : dispatch_mb<3, 8, IDIFF_CONV_UPSAMPLE2>(a, p.twl, p.mb, p.vecw, st);
+            else if (d->ks == 1)
+                rc = normal ? dispatch_mb<1, 16, IDIFF_CONV_NORMAL>(a, p.twl, p.mb, p.vecw, st) : dispatch_mb<1, 16, IDIFF_CONV_UNSHUFFLE2>(a, p.twl, p.mb, p.vecw, st);
+            else
+                rc = dispatch_mb<7, 2, IDIFF_CONV_NORMAL>(a, p.twl, p.mb, p.vecw, st);
+    }
+    // the separate finalize launch behind kernels without the fused tail
+    if (rc != IDIFF_OK || !d->gn_out_a) return rc;
+    return idiff_gn_finalize(d->stats, a.ntiles, a.B, a.Cout, d->gn_groups, a.Hout * a.Wout, d->gn_gamma, d->gn_beta, d->gn_film, d->gn_film_ld,
+                             d->gn_eps, d->gn_out_a, d->gn_out_b, d->gn_mean_rstd, stream);
+}
 
-extern "C" int idiff_conv2d_plan(const idiff_conv_desc* d) {
-    const int keep = g_last_algo;
-    const int rc = conv2d_run(d, nullptr, true);
-    const int algo = g_last_algo;
-    g_last_algo = keep;  // idiff_conv2d_last_algo() keeps speaking of launches
-    return rc != IDIFF_OK ? rc : algo;
+extern "C" int idiff_conv2d_fwd(const idiff_conv_desc* d, idiff_stream_t stream) {
+    ConvPlan p;
+    if (const int rc = conv2d_args(d, &p)) return rc;
+    if (const int rc = conv2d_choose(d, &p)) return rc;
+    g_last_algo = p.algo;
+    return conv2d_launch(d, p, stream);
+}
+
+extern "C" int idiff_conv2d_plan(const idiff_conv_desc* d) {  // idiff_conv2d_last_algo() keeps speaking of launches
+    ConvPlan p;
+    if (const int rc = conv2d_args(d, &p)) return rc;
+    if (const int rc = conv2d_choose(d, &p)) return rc;
+    return p.algo;
 }
 
 static int pack_common(const float* w, float* wpk, int Cout, int Cin, int ks, int tr, idiff_stream_t stream) {

@@ -286,25 +286,6 @@ __global__ __launch_bounds__(256) void wgrad1x1_kernel(const WgArgs a) {
     }
 }
 
-inline bool wgrad1x1_eligible(const WgArgs& a, int ks, int mode) {
-    if (ks != 1 || mode == IDIFF_CONV_UPSAMPLE2 || a.pro_a) return false;
-    if (mode == IDIFF_CONV_UNSHUFFLE2 && (a.Wout % 4 || a.src1)) return false;
-    if (a.Cout % 64 || ((long long)a.Hout * a.Wout) % W1_PX) return false;
-    if (a.src1 && a.C0v % 64) return false;
-    if ((reinterpret_cast<uintptr_t>(a.src0) & 15) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || (reinterpret_cast<uintptr_t>(a.dy) & 15)) return false;
-    if (a.bs0 % 4 || (a.src1 && a.bs1 % 4) || a.dybs % 4) return false;
-    return true;
-}
-inline void wgrad1x1_geometry(int Cin, int Cout, int B, int HW, int* ncob, int* ncib, int* nsplit) {
-    *ncob = Cout / 64;
-    *ncib = (Cin + 63) / 64;
-    const int total = B * (HW / W1_PX);
-    int s = 1024 / (*ncob * *ncib);  // ~2 resident workgroups per CU, two rounds
-    if (s < 1) s = 1;
-    if (s > total) s = total;
-    *nsplit = s;
-}
-
 // dW[co][ci][tap] (+)= sum_s ws[s][tap][ci][co]   (fixed order -> deterministic)
 // One workgroup owns 1024/KL consecutive elements of the [tap][ci][co] image: thread = (4 consecutive elements, split lane kl); it adds
 // the splits kl, kl+KL, .. with 16-byte loads (four in flight), the KL lane sums are then added in lane order through LDS.  The
@@ -388,6 +369,48 @@ inline void wg_geometry(int ks, int Cin, int Cout, int B, int Hout, int Wout, in
     *nsplit = s;
 }
 
+// The streaming 1x1 kernel (wgrad1x1_kernel above).  Below launch_wgrad_reduce on purpose: kernels land in the code object in the
+// order of their first use, and that order is kept so the device code stays comparable byte for byte across host-side changes.
+inline bool wgrad1x1_eligible(const WgArgs& a, int ks, int mode) {
+    if (ks != 1 || mode == IDIFF_CONV_UPSAMPLE2 || a.pro_a) return false;
+    if (mode == IDIFF_CONV_UNSHUFFLE2 && (a.Wout % 4 || a.src1)) return false;
+    if (a.Cout % 64 || ((long long)a.Hout * a.Wout) % W1_PX) return false;
+    if (a.src1 && a.C0v % 64) return false;
+    if ((reinterpret_cast<uintptr_t>(a.src0) & 15) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || (reinterpret_cast<uintptr_t>(a.dy) & 15)) return false;
+    if (a.bs0 % 4 || (a.src1 && a.bs1 % 4) || a.dybs % 4) return false;
+    return true;
+}
+inline void wgrad1x1_geometry(int Cin, int Cout, int B, int HW, int* ncob, int* ncib, int* nsplit) {
+    *ncob = Cout / 64;
+    *ncib = (Cin + 63) / 64;
+    const int total = B * (HW / W1_PX);
+    int s = 1024 / (*ncob * *ncib);  // ~2 resident workgroups per CU, two rounds
+    if (s < 1) s = 1;
+    if (s > total) s = total;
+    *nsplit = s;
+}
+inline int launch_wgrad1x1(const WgArgs& a, int mode, hipStream_t st) {
+    const size_t lds = (size_t)2 * 64 * W1_LD * sizeof(float);
+    const bool unsh = mode == IDIFF_CONV_UNSHUFFLE2;
+    auto kern = unsh ? wgrad1x1_kernel<true> : wgrad1x1_kernel<false>;
+    static idiff_dyn_lds_cache attr[2];
+    if (const int rc = idiff_dyn_lds(attr[unsh], kern, lds, "conv2d_wgrad")) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.ncob * a.nchunks * a.nsplit), dim3(256), lds, st, a);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad(1x1): %s", hipGetErrorString(le));
+    return IDIFF_OK;
+}
+
+template <int KS, int CK, int TWL, int MODE, bool THIN>
+int launch_wg_tw(const WgArgs& a, size_t lds, hipStream_t st) {
+    static idiff_dyn_lds_cache lds_cache;
+    auto kern = conv_wgrad_kernel<KS, CK, TWL, MODE, THIN>;
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d_wgrad")) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.nchunks * a.ncob * a.nsplit), dim3(256), lds, st, a);
+    IDIFF_CHECK_LAUNCH("conv2d_wgrad");
+    return IDIFF_OK;
+}
+
 template <int KS, int CK, int MODE, bool THIN = false>
 int launch_wg(const WgArgs& a, int twl, hipStream_t st) {
     const int TW = 1 << twl, TH = 128 / TW;
@@ -397,23 +420,9 @@ int launch_wg(const WgArgs& a, int twl, hipStream_t st) {
     const size_t ot = (size_t)NB * 16 * 65;
     if (ot > fl) fl = ot;
     const size_t lds = fl * sizeof(float);
-    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "conv2d_wgrad: LDS budget exceeded");
-    dim3 grid(a.nchunks * a.ncob * a.nsplit);
-#define IDIFF_WG_LAUNCH(TWL)                                                                                             \
-    {                                                                                                                    \
-        static size_t attr = 0;                                                                                          \
-        auto kern = conv_wgrad_kernel<KS, CK, TWL, MODE, THIN>;                                                           \
-        if (lds > attr) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e)); \
-            attr = lds;                                                                                                  \
-        }                                                                                                                \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);                                                           \
-    }
-    if (twl == 5) IDIFF_WG_LAUNCH(5) else if (twl == 4) IDIFF_WG_LAUNCH(4) else IDIFF_WG_LAUNCH(3)
-#undef IDIFF_WG_LAUNCH
-    IDIFF_CHECK_LAUNCH("conv2d_wgrad");
-    return IDIFF_OK;
+    if (twl == 5) return launch_wg_tw<KS, CK, 5, MODE, THIN>(a, lds, st);
+    if (twl == 4) return launch_wg_tw<KS, CK, 4, MODE, THIN>(a, lds, st);
+    return launch_wg_tw<KS, CK, 3, MODE, THIN>(a, lds, st);
 }
 
 }  // namespace
@@ -423,9 +432,9 @@ extern "C" int idiff_conv2d_wgrad_last_algo(void) { return g_last_wgrad_algo; }
 
 extern "C" int64_t idiff_conv2d_wgrad_ws_floats(const idiff_conv_desc* d) {
     if (!d) return -1;
-    const int Cin = (d->mode == IDIFF_CONV_UNSHUFFLE2 ? d->C0 * 4 : d->C0) + d->C1;
-    const int Hout = d->mode == IDIFF_CONV_UPSAMPLE2 ? d->Hin * 2 : (d->mode == IDIFF_CONV_UNSHUFFLE2 ? d->Hin / 2 : d->Hin);
-    const int Wout = d->mode == IDIFF_CONV_UPSAMPLE2 ? d->Win * 2 : (d->mode == IDIFF_CONV_UNSHUFFLE2 ? d->Win / 2 : d->Win);
+    idiff_detail::ConvShape s;
+    idiff_detail::conv_shape(d, &s);  // an answer for every descriptor: the rules are the entry point's to enforce
+    const int Cin = s.Cin, Hout = s.Hout, Wout = s.Wout;
     int ck, nch, ncob, nt, tx, ns;
     long long bf16_ws = 0;
     wg_geometry(d->ks, Cin, d->Cout, d->B, Hout, Wout, &ck, &nch, &ncob, &nt, &tx, &ns);
@@ -438,14 +447,16 @@ extern "C" int64_t idiff_conv2d_wgrad_ws_floats(const idiff_conv_desc* d) {
         Wout % 32 == 0) {  // the bf16-operand form: its own partials
         bf16_ws = idiff_detail::bf16_wgrad_ws_floats(Cin, d->Cout, d->B, Hout, Wout);
     }
-    if (d->ks == 3 && d->Cout % 64 == 0) {  // the Winograd kernels may take this shape with their own split counts
+    // the Winograd kernels that may take this shape, with their own split counts
+    if (idiff_detail::wino_wgrad_shape(d->ks, d->Cout)) {
         int wcob, wcib, wns;
         idiff_detail::wino_wgrad_geometry(Cin, d->Cout, d->B, Hout, Wout, &wcob, &wcib, &wns);
         if (wns > ns) ns = wns;
-        if (Hout % 4 == 0 && Wout % 16 == 0) {
-            idiff_detail::wino4_wgrad_geometry(Cin, d->Cout, d->B, Hout, Wout, &wcob, &wcib, &wns);
-            if (wns > ns) ns = wns;
-        }
+    }
+    if (idiff_detail::wino4_wgrad_shape(d->ks, d->Cout, Hout, Wout)) {
+        int wcob, wcib, wns;
+        idiff_detail::wino4_wgrad_geometry(Cin, d->Cout, d->B, Hout, Wout, &wcob, &wcib, &wns);
+        if (wns > ns) ns = wns;
     }
     const int64_t f32_ws = (int64_t)ns * d->ks * d->ks * Cin * d->Cout;
     return bf16_ws > f32_ws ? bf16_ws : f32_ws;
@@ -458,51 +469,19 @@ extern "C" int idiff_conv2d_wgrad(const idiff_conv_desc* d, const float* dy, int
     IDIFF_CHECK_ARG(d->ks == 1 || d->ks == 3 || d->ks == 7, "conv2d_wgrad: ks must be 1, 3 or 7");
     IDIFF_CHECK_ARG((d->C1 > 0) == (d->src1 != nullptr), "conv2d_wgrad: src1/C1 mismatch");
     IDIFF_CHECK_ARG(!(d->pro_a && d->C1 > 0), "conv2d_wgrad: prologue needs a single source");
-    WgArgs a;
-    a.src0 = d->src0;
-    a.src1 = d->src1;
-    a.bs0 = d->src0_bstride;
-    a.bs1 = d->src1_bstride;
-    a.B = d->B;
-    a.C0r = d->C0;
-    a.Hin = d->Hin;
-    a.Win = d->Win;
-    a.Cout = d->Cout;
-    a.pro_a = d->pro_a;
-    a.pro_b = d->pro_b;
-    a.dy = dy;
-    a.dybs = dy_bstride;
-    a.ws = ws;
-    if (d->mode == IDIFF_CONV_UNSHUFFLE2) {
-        IDIFF_CHECK_ARG(d->ks == 1 && d->C1 == 0, "conv2d_wgrad: unshuffle mode needs ks=1 and a single source");
-        a.C0v = d->C0 * 4;
-        a.C1v = 0;
-        a.Hout = d->Hin / 2;
-        a.Wout = d->Win / 2;
-    } else if (d->mode == IDIFF_CONV_UPSAMPLE2) {
-        a.C0v = d->C0;
-        a.C1v = d->C1;
-        a.Hout = d->Hin * 2;
-        a.Wout = d->Win * 2;
-    } else {
-        a.C0v = d->C0;
-        a.C1v = d->C1;
-        a.Hout = d->Hin;
-        a.Wout = d->Win;
-    }
-    a.Cin = a.C0v + a.C1v;
-    IDIFF_CHECK_ARG(dy_bstride >= (long long)d->Cout * a.Hout * a.Wout, "conv2d_wgrad: dy_bstride too small");
+    idiff_detail::ConvShape s;
+    if (const char* why = idiff_detail::conv_shape(d, &s)) IDIFF_FAIL(IDIFF_E_BADARG, "conv2d_wgrad: %s", why);
+    IDIFF_CHECK_ARG(dy_bstride >= (long long)d->Cout * s.Hout * s.Wout, "conv2d_wgrad: dy_bstride too small");
+    WgArgs a;                // the f32 kernels of this file
+    idiff_detail::WwArgs w;  // the Winograd and bf16-operand kernels
+    idiff_detail::fill_wgrad_head(a, d, s, dy, dy_bstride, ws);
+    idiff_detail::fill_wgrad_head(w, d, s, dy, dy_bstride, ws);
+    w.ups = d->mode == IDIFF_CONV_UPSAMPLE2 ? 1 : 0;
     int ck;
     wg_geometry(d->ks, a.Cin, a.Cout, a.B, a.Hout, a.Wout, &ck, &a.nchunks, &a.ncob, &a.ntiles, &a.tiles_x, &a.nsplit);
     const int twl = wg_pick_twl(a.Wout);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    idiff_detail::WwArgs w;
-    w.src0 = a.src0, w.src1 = a.src1, w.bs0 = a.bs0, w.bs1 = a.bs1;
-    w.C0v = a.C0v, w.C1v = a.C1v, w.C0r = a.C0r, w.Cin = a.Cin;
-    w.B = a.B, w.Hin = a.Hin, w.Win = a.Win, w.Hout = a.Hout, w.Wout = a.Wout, w.Cout = a.Cout;
-    w.pro_a = a.pro_a, w.pro_b = a.pro_b, w.dy = a.dy, w.dybs = a.dybs, w.ws = a.ws;
-    w.ups = d->mode == IDIFF_CONV_UPSAMPLE2 ? 1 : 0;
     g_last_wgrad_algo = IDIFF_CONV_ALGO_DIRECT;
     IDIFF_CHECK_ARG(d->operands == 0 || d->operands == 1, "conv2d_wgrad: bad operands %d", d->operands);
     if (d->operands == 1 && idiff_detail::bf16_wgrad_eligible(w, d->ks, d->mode)) {
@@ -522,20 +501,8 @@ extern "C" int idiff_conv2d_wgrad(const idiff_conv_desc* d, const float* dy, int
     } else if (wgrad1x1_eligible(a, d->ks, d->mode)) {
         g_last_wgrad_algo = IDIFF_CONV_ALGO_STREAM1X1;
         wgrad1x1_geometry(a.Cin, a.Cout, a.B, a.Hout * a.Wout, &a.ncob, &a.nchunks, &a.nsplit);
-        const size_t lds = (size_t)2 * 64 * W1_LD * sizeof(float);
-        const bool unsh = d->mode == IDIFF_CONV_UNSHUFFLE2;
-        auto kern = unsh ? wgrad1x1_kernel<true> : wgrad1x1_kernel<false>;
-        static idiff_dyn_lds_cache attr[2];
-        {
-            hipError_t e = idiff_ensure_dyn_lds(attr[unsh], reinterpret_cast<const void*>(kern), lds);
-            if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        hipLaunchKernelGGL(kern, dim3(a.ncob * a.nchunks * a.nsplit), dim3(256), lds, st, a);
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad(1x1): %s", hipGetErrorString(le));
-        rc = IDIFF_OK;
-    } else if (d->ks == 3) {
-        IDIFF_CHECK_ARG(d->mode != IDIFF_CONV_UNSHUFFLE2, "conv2d_wgrad: unshuffle needs ks=1");
+        rc = launch_wgrad1x1(a, d->mode, st);
+    } else if (d->ks == 3) {  // (not unshuffle: conv_shape)
         if (d->mode == IDIFF_CONV_NORMAL && a.Cin <= 8)
             rc = a.Cout <= 16 ? launch_wg<3, 8, IDIFF_CONV_NORMAL, true>(a, twl, st) : launch_wg<3, 8, IDIFF_CONV_NORMAL>(a, twl, st);
         else if (d->mode == IDIFF_CONV_NORMAL && a.Cout <= 16)

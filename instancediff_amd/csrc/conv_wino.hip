@@ -467,13 +467,9 @@ __global__ __launch_bounds__(NT) void conv_wino_kernel(const ConvArgs a TRACE_PA
 template <int MODE, int SPEC, bool RAG>
 int launch_rag(const ConvArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)2 * R_FLOATS + 2 * V_FLOATS + 2 * U_FLOATS + 256 + (SPEC == 2 ? 4 * (size_t)a.C0r : 0)) * sizeof(float);
-    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "conv2d(winograd): LDS budget exceeded (%zu bytes)", lds);
     static idiff_dyn_lds_cache lds_cache;
     auto kern = conv_wino_kernel<MODE, SPEC, RAG>;
-    {
-        hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d(winograd)")) return rc;
     int num_cu = 0;
     if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd): cannot query the CU count");
     const int total = (int)a.total_wg;

@@ -328,13 +328,9 @@ __global__ __launch_bounds__(NT) void wino4_wgrad_kernel(const WwArgs a) {
 template <bool PRO>
 int launch(const WwArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)R_FLOATS + 2 * D_FLOATS + 2 * E_FLOATS + NL * NT + (PRO ? 2 * (size_t)a.C0r : 0)) * sizeof(float);
-    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "conv2d_wgrad(winograd4): LDS budget exceeded (%zu bytes)", lds);
     static idiff_dyn_lds_cache lds_cache;
     auto kern = wino4_wgrad_kernel<PRO>;
-    {
-        hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad(winograd4): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d_wgrad(winograd4)")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.ncob * a.ncib * a.nsplit), dim3(NT), lds, st, a);
     IDIFF_CHECK_LAUNCH("conv2d_wgrad(winograd4)");
     return IDIFF_OK;
@@ -352,11 +348,13 @@ bool wino4_wgrad_disabled() {  // IDIFF_WGRAD4=0: weight gradients stay on the F
 
 namespace idiff_detail {
 
+bool wino4_wgrad_shape(int ks, int Cout, int Hout, int Wout) { return ks == 3 && Cout % 64 == 0 && Hout % 4 == 0 && Wout % 16 == 0; }
+
 bool wino4_wgrad_eligible(const WwArgs& a, int ks, int mode) {
-    if (ks != 3 || wino4_wgrad_disabled()) return false;
+    if (!wino4_wgrad_shape(ks, a.Cout, a.Hout, a.Wout) || wino4_wgrad_disabled()) return false;
     if (mode != IDIFF_CONV_NORMAL && mode != IDIFF_CONV_UPSAMPLE2) return false;
     if (mode == IDIFF_CONV_UPSAMPLE2 && (a.src1 || a.pro_a)) return false;
-    if (a.Cout % 64 || a.Cin % 16 || a.Hout % 4 || a.Wout % 16) return false;
+    if (a.Cin % 16) return false;
     if (a.src1 && a.C0v % CIB) return false;
     if (a.pro_a && a.src1) return false;
     if ((reinterpret_cast<uintptr_t>(a.dy) & 15) || (a.dybs & 3) || (a.Wout & 3)) return false;  // float4 dY loads

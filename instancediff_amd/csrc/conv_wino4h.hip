@@ -422,10 +422,7 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)2 * R_FLOATS + 2 * V_FLOATS + 256 + NL * NT) * sizeof(float);  // 44 KB: two workgroups per CU
     static idiff_dyn_lds_cache lds_cache;
     auto kern = conv_wino4h_kernel<MODE, SPEC, RAG>;
-    {
-        hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4h): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d(winograd4h)")) return rc;
     int num_cu = 0;
     if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4h): cannot query the CU count");
     Geo4h g;

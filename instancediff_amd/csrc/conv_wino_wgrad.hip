@@ -316,13 +316,9 @@ __global__ __launch_bounds__(NT) void wino_wgrad_kernel(const WwArgs a) {
 template <int MODE, bool PRO>
 int launch(const WwArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)R_FLOATS + 4 * OP_FLOATS + (PRO ? 2 * (size_t)a.C0r : 0)) * sizeof(float);
-    if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "conv2d_wgrad(winograd): LDS budget exceeded (%zu bytes)", lds);
     static idiff_dyn_lds_cache lds_cache;
     auto kern = wino_wgrad_kernel<MODE, PRO>;
-    {
-        hipError_t e = idiff_ensure_dyn_lds(lds_cache, reinterpret_cast<const void*>(kern), lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "conv2d_wgrad(winograd): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
+    if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d_wgrad(winograd)")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.ncob * a.ncib * a.nsplit), dim3(NT), lds, st, a);
     IDIFF_CHECK_LAUNCH("conv2d_wgrad(winograd)");
     return IDIFF_OK;
@@ -332,10 +328,12 @@ int launch(const WwArgs& a, hipStream_t st) {
 
 namespace idiff_detail {
 
+bool wino_wgrad_shape(int ks, int Cout) { return ks == 3 && Cout % 64 == 0; }
+
 bool wino_wgrad_eligible(const WwArgs& a, int ks, int mode) {
-    if (ks != 3 || winograd_disabled()) return false;
+    if (!wino_wgrad_shape(ks, a.Cout) || winograd_disabled()) return false;
     if (mode != IDIFF_CONV_NORMAL && mode != IDIFF_CONV_UPSAMPLE2) return false;
-    if (a.Cout % 64 || a.Cin % 16 || a.Hout % 2 || a.Wout % 16) return false;
+    if (a.Cin % 16 || a.Hout % 2 || a.Wout % 16) return false;
     if (a.src1 && a.C0v % 64) return false;
     if (mode == IDIFF_CONV_UPSAMPLE2 && (a.pro_a || a.src1)) return false;
     if (a.pro_a && a.src1) return false;

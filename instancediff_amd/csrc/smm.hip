@@ -703,12 +703,9 @@ extern "C" int idiff_linear_t_grouped_fwd(const idiff_linear_group* groups, int 
     }
     const size_t lds = ((size_t)LM_ROWS * (kmax + LM_KPAD) + (size_t)LM_WAVES * 4 * 64 * 4) * sizeof(float);
     IDIFF_CHECK_ARG(lds <= 160 * 1024, "linear_t_grouped: K too large (%d)", kmax);
-    static size_t attr = 0;
-    if (lds > 64 * 1024 && lds > attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_t_mfma_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "linear_t_grouped: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = lds;
-    }
+    static idiff_dyn_lds_cache attr;
+    if (lds > 64 * 1024)
+        if (const int rc = idiff_dyn_lds(attr, linear_t_mfma_grouped_kernel, lds, "linear_t_grouped")) return rc;
     hipLaunchKernelGGL(linear_t_mfma_grouped_kernel, dim3(gx, gy, ngroups), dim3(512), lds, (hipStream_t)stream, args);
     IDIFF_CHECK_LAUNCH("linear_t_grouped_fwd");
     return IDIFF_OK;
@@ -721,12 +718,8 @@ extern "C" int idiff_smm_memproj_fwd(const float* feat, int64_t feat_bstride, co
     IDIFF_CHECK_ARG(B > 0 && N > 0 && C >= 2 && C % 2 == 0 && C <= 512, "smm_memproj: C must be even and <= 512 (got %d)", C);
     IDIFF_CHECK_ARG(N % 4 == 0 && feat_bstride % 4 == 0, "smm_memproj: N and feat_bstride must be multiples of 4");
     const size_t lds = (size_t)(C * MP_PX + 4 * MP_PX + 2 * MP_PX) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smm_memproj_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "smm_memproj: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = lds;
-    }
+    static idiff_dyn_lds_cache attr;
+    if (const int rc = idiff_dyn_lds(attr, smm_memproj_kernel, lds, "smm_memproj")) return rc;
     hipLaunchKernelGGL(smm_memproj_kernel, dim3((N + MP_PX - 1) / MP_PX, B), dim3(256), lds, (hipStream_t)stream, feat, (long long)feat_bstride,
                        ln1_g, ln1_b, wpk, bias, ln2_g, ln2_b, out, C, N, eps);
     IDIFF_CHECK_LAUNCH("smm_memproj_fwd");
@@ -782,12 +775,8 @@ extern "C" int idiff_smm_memproj_compact_bwd(const float* feat, int64_t feat_bst
     const int ntx = (N + MP_PX - 1) / MP_PX, ntiles = B * ntx, grid = memproj_bwd_grid(B, N);
     const int PW = C * C + 3 * C + 1;
     const size_t lds = (size_t)(3 * C * MB_LD + 16 * 64) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smm_memproj_gram_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "smm_memproj_compact_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = true;
-    }
+    static idiff_dyn_lds_cache attr;
+    if (const int rc = idiff_dyn_lds(attr, smm_memproj_gram_bwd_kernel, lds, "smm_memproj_compact_bwd")) return rc;
     hipLaunchKernelGGL(smm_memproj_gram_bwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, feat, (long long)feat_bstride, ln1_g, ln1_b, gram,
                        hvec, evar_dev, dm, dfeat, (long long)dfeat_bstride, ws, N, Cm, ntx, ntiles, eps1, eps2);
     IDIFF_CHECK_LAUNCH("smm_memproj_compact_bwd");
@@ -832,12 +821,9 @@ static int linear_t_launch(const float* x, int64_t ldx, const float* wT, int64_t
     const size_t lds_m = ((size_t)LM_ROWS * (K + LM_KPAD) + (size_t)LM_WAVES * 4 * 64 * 4) * sizeof(float);
     if (!mfma_off && N % 4 == 0 && ldw % 4 == 0 && w_hs % 4 == 0 && (reinterpret_cast<uintptr_t>(wT) & 15) == 0 && lds_m <= 160 * 1024) {
         dim3 gridm((N + 63) / 64, (R + LM_ROWS - 1) / LM_ROWS, heads);
-        static size_t attr_m = 0;
-        if (lds_m > 64 * 1024 && lds_m > attr_m) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_t_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
-            if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "linear_t_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_m = lds_m;
-        }
+        static idiff_dyn_lds_cache attr_m;
+        if (lds_m > 64 * 1024)
+            if (const int rc = idiff_dyn_lds(attr_m, linear_t_mfma_kernel, lds_m, "linear_t_fwd")) return rc;
         hipLaunchKernelGGL(linear_t_mfma_kernel, gridm, dim3(512), lds_m, (hipStream_t)stream, x, (long long)ldx, wT, (long long)ldw, bias, res,
                            (long long)ldr, gscale, out, (long long)ldo, R, K, N, act_in, act_out, (long long)x_hs, (long long)w_hs,
                            (long long)b_hs, (long long)o_hs, ln_g, ln_b, ln_eps);
@@ -848,12 +834,9 @@ static int linear_t_launch(const float* x, int64_t ldx, const float* wT, int64_t
     const size_t lds = ((size_t)LT_ROWS * K + 4 * LT_ROWS * 64) * sizeof(float);
     // the kernel stages LT_ROWS rows of K floats: beyond K = 4864 that is more than the 160 KiB of LDS a workgroup can have
     if (lds > 160 * 1024) IDIFF_FAIL(IDIFF_E_UNSUPPORTED, "linear_t_fwd: K = %d needs %zu bytes of LDS (K <= 4864)", K, lds);
-    static size_t attr = 0;
-    if (lds > 64 * 1024 && lds > attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_t_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) IDIFF_FAIL(IDIFF_E_HIP, "linear_t_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr = lds;
-    }
+    static idiff_dyn_lds_cache attr;
+    if (lds > 64 * 1024)
+        if (const int rc = idiff_dyn_lds(attr, linear_t_kernel, lds, "linear_t_fwd")) return rc;
     hipLaunchKernelGGL(linear_t_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, (long long)ldx, wT, (long long)ldw, bias, res,
                        (long long)ldr, gscale, out, (long long)ldo, R, K, N, act_in, act_out, (long long)x_hs, (long long)w_hs, (long long)b_hs,
                        (long long)o_hs, ln_g, ln_b, ln_eps);
