@@ -94,8 +94,22 @@ struct Geo4 {
 // request crosses over), so an item's main loop starts right behind its predecessor's epilogue -- no fill (9 k cycles of an 83 k
 // item at Cin = 64), no barrier at the item's top -- and its first chunk waits for nothing younger than the epilogue's 128 KB of
 // stores (their drain overlaps the first chunks).  A workgroup without a next item streams through zero-record resources.
-template <int MODE, int SPEC, bool RAG, bool HEAVY>
+//
+// G16 (normal mode, SPEC 1 / 3, 16-byte aligned sources: launch_rag): the patch is gathered in 16-byte pieces.  R keeps its strides but
+// its column origin lies three floats to the left (row float 3 + c = patch column c: gather_decode16), so a slot of 768 float4 is 12
+// `buffer_load_dwordx4 ... offen lds` wave-instructions at the CU's one address unit instead of 48.  Same bytes in the same multiplies
+// and adds: the results are the dword gather's bit for bit.  Measured (profiles/r23): the count alone is worth 0 - 3 %; who issues the
+// pieces is worth more.  The light waves set a chunk's length and the heavy waves reach its barrier 1.0 - 1.4 k cycles early, so here
+// the heavy waves issue all 12 gather pieces and a fifth weight piece (5 + 3 pieces per chunk, light waves 4 + 0): 64 -> 64 at 256^2
+// 237 -> 224 us, 144 -> 64 477 -> 463.  Six or more weight pieces per heavy wave, or s_setprio for the light ones, lose it again.
+template <int MODE, int SPEC, bool RAG, bool HEAVY, bool G16>
 __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g, float* smem TRACE_PARAM) {
+    static_assert(!G16 || (MODE == IDIFF_CONV_NORMAL && SPEC != 2), "the 16-byte gather: contiguous pieces, LDS-DMA only");
+    // 1-KB LDS-DMA pieces per wave and chunk: N_U of the 36 weight pieces, NR gather requests (dword gather: NL, 256 bytes each).
+    // G16 deals its 12 gather pieces and the weight pieces by class: HU / HR per heavy wave, 9 - HU / 3 - HR per light wave
+    constexpr int HU = G16 ? 5 : 4, HR = 3;
+    constexpr int N_U = HEAVY ? HU : 9 - HU;
+    constexpr int NR = G16 ? (HEAVY ? HR : 3 - HR) : NL;
     float* const Rb = smem;                   // [3][R_FLOATS]
     float* const Vb = smem + 3 * R_FLOATS;    // [2][V_FLOATS]
     float* const Ub = Vb + 2 * V_FLOATS;      // [2][U_FLOATS]
@@ -112,6 +126,8 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     const int k4 = lane >> 4;  // k index of the MFMA operands (lane & 15: tile of the B operand / channel of the A operand)
     const int cb = wave & 3;   // MFMA role: 16-channel block
     const int tblk = wave >> 2;  // MFMA role: upper / lower 8x32 half-patch
+    // G16: piece i of a wave is piece first + 4 i of the chunk's 36 (weights) / of the slot's 12 (gather); the heavy waves' come first
+    const int g16_u0 = HEAVY ? wave : 4 * HU + wave - 4, g16_r0 = HEAVY ? wave : 4 * HR + wave - 4;
     const int HWin = a.Hin * a.Win;
     const int nchunks = a.Cin / CK;  // even, >= 4 (Cin % 8 == 0, Cin >= 16: conv_wino4_items)
 
@@ -169,7 +185,8 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     // (thread-private entries); returns the item's padding mask.
     auto write_table = [&](const View& v) {
         unsigned om;
-        gather_decode<MODE, NT, NL, PSP, PS, RS, RCOLS>(tid, om, v.y0, v.x0, a, gtab, HWin);
+        if (G16) gather_decode16<NT, NR, 256, PSP / 4, PS / 4, RS / 4>(tid, g16_r0 * 64 + lane, om, v.y0, v.x0, a, gtab, HWin);
+        else gather_decode<MODE, NT, NL, PSP, PS, RS, RCOLS>(tid, om, v.y0, v.x0, a, gtab, HWin);
         return om;
     };
     auto shift_B_to_A = [&]() { p0A = p0B, p1A = p1B, puA = puB, vA = vB, omaskA = omaskB; };
@@ -200,7 +217,21 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     // reads it as descriptor or soffset needs five wait states hipcc's hazard recognizer does not insert for inline asm.
     // The 2304 float4 of weight chunk p -> U[buf]: four 1-KB pieces per wave, the last 256 float4 by the light waves.
     const unsigned u_voff = tid * 16;
+    const unsigned l_voff = lane * 16;
+    auto dma_u_piece16 = [&](int p, int buf, int i) {  // G16: 1-KB piece g16_u0 + 4 i of the chunk
+        const bool inA = p < nchunks;
+        const unsigned ub = (unsigned)(g16_u0 + 4 * i) * 1024u;
+        const int so = (inA ? p : p - nchunks) * ustride_b + (int)ub;
+        const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inA ? puA : puB), 0, inA ? 0x7fffffff : nrB, RSRC_FLAGS);
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane(U_LDS0 + (unsigned)buf * U_BYTES + ub);
+        asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(l_voff), "s"(rsu), "s"(lds0), "s"(so) : "memory");
+    };
     auto dma_u = [&](int p, int buf) {
+        if (G16) {
+#pragma unroll
+            for (int i = 0; i < N_U; ++i) dma_u_piece16(p, buf, i);
+            return;
+        }
         const bool inA = p < nchunks;
         const int so = (inA ? p : p - nchunks) * ustride_b;
         const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inA ? puA : puB), 0, inA ? 0x7fffffff : nrB, RSRC_FLAGS);
@@ -222,6 +253,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     // one 1-KB piece of the same copy: i = 0..3, and 4 = the light waves' fifth.  Between two barriers a chunk's pieces are dealt
     // out one per quad: eight waves issuing 36 of them at once right behind the barrier held the last wave in line ~1 k cycles
     auto dma_u_piece = [&](int p, int buf, int i) {
+        if (G16) return dma_u_piece16(p, buf, i);
         const bool inA = p < nchunks;
         const int so = (inA ? p : p - nchunks) * ustride_b + (i < 4 ? i * NT * 16 : 4 * NT * 16 - 256 * 16);
         const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inA ? puA : puB), 0, inA ? 0x7fffffff : nrB, RSRC_FLAGS);
@@ -264,8 +296,21 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
         const float* const base = reinterpret_cast<const float*>(second ? b1 : b0);
         const int so = (second ? cbase - C0v : cbase) * HWin * 4;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, inA ? 0x7fffffff : nrB, RSRC_FLAGS);
+        if (G16) {  // 64 float4 slots: 1 KB per wave-instruction
+            const unsigned lds16 = __builtin_amdgcn_readfirstlane(lds_base + rslot + (unsigned)(g16_r0 + 4 * i) * 1024u);
+            asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(goff_i), "s"(rs), "s"(so), "s"(lds16) : "memory");
+            return;
+        }
         const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_base + rslot + (unsigned)wave * 256u + (unsigned)i * 2048u);
         asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %0, %1, %2 offen lds" ::"v"(goff_i), "s"(rs), "s"(so), "s"(lds0) : "memory");
+    };
+    auto dma_raw_fill = [&](int p, unsigned rslot) {  // a whole position at once: the fill
+        if (G16) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) dma_raw_piece(p, rslot, i, gtab[i * NT + tid]);
+        } else {
+            dma_raw(p, rslot);
+        }
     };
     // SPEC 2 (GroupNorm/FiLM affine + SiLU applied while the patch is staged): the VALU has to touch every element anyway, so this
     // form keeps the register path -- plain buffer loads into rinA / rinB (even / odd positions), activation in registers, one
@@ -294,7 +339,6 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
             R[i * NT] = ((om >> i) & 1u) ? 0.f : x;
         }
     };
-    constexpr int N_U = HEAVY ? 4 : 5;  // 1-KB weight copies per wave and chunk
 
     // ---- input transform B^T d B of an R slot -> V[buf].  Thread = (ci = k4, tile (tyl, tx) of half-patch thalf) x row set:
     //   heavy waves 0-3: Winograd rows (1,2) (trole 0) or (3,4) (trole 1):  X = d4 + al*d2, Y = d3 + al*d1, rows X +- be*Y
@@ -311,27 +355,50 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     // P = 4*dA - 5*dB) and reads (d1, d3 | dC); T2 finishes the role's Winograd rows of B^T d; T3 / T4 apply B^T along the
     // columns of one row each and write its three position pairs
     float ta[6], tb[6], tlo[6], thi[6];
-    auto rd_row = [&](const float* p, float (&d)[6]) {
+    // G16: a tile's six columns are row floats 4tx + 3 .. 4tx + 8: the last float of slot tx, slot tx + 1, the first float of slot
+    // tx + 2 -- three aligned ds_read_b128, conflict-free by the argument of RS / PSP above (a whole-slot shift changes no bank
+    // pattern): 12 LDS cycles a row.  The two outer floats as b32 (32 banks: channel AND row stride 0, four-way within a 32-lane
+    // group) would take 8 cycles each -- and hipcc narrows a vector load of which one element is used to exactly that, so the outer
+    // slots travel whole (Row16) and are made opaque where the row is consumed, a piece later.
+    struct Row16 {
+        floatx4 lo, mid, hi;
+    };
+    Row16 ra, rb;
+    auto rd_row = [&](const float* p, float (&d)[6], Row16& w) {
+        if (G16) {
+            w.lo = *reinterpret_cast<const floatx4*>(p);
+            w.mid = *reinterpret_cast<const floatx4*>(p + 4);
+            w.hi = *reinterpret_cast<const floatx4*>(p + 8);
+            return;
+        }
         const floatx4 lo = *reinterpret_cast<const floatx4*>(p);
         const floatx2 hi = *reinterpret_cast<const floatx2*>(p + 4);
         d[0] = lo.x, d[1] = lo.y, d[2] = lo.z, d[3] = lo.w, d[4] = hi.x, d[5] = hi.y;
     };
+    auto take_row = [&](float (&d)[6], Row16& w) {  // G16: the row read a piece ago
+        if (!G16) return;
+        asm volatile("" : "+v"(w.lo), "+v"(w.hi));
+        d[0] = w.lo.w, d[1] = w.mid.x, d[2] = w.mid.y, d[3] = w.mid.z, d[4] = w.mid.w, d[5] = w.hi.x;
+    };
     auto tr_piece = [&](int piece, unsigned rslot, int buf) {
         const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(trbase) + rslot);
         if (piece == 0) {
-            if (heavy) rd_row(p + 1 * RS, ta), rd_row(p + 3 * RS, tb);  // d2, d4
-            else rd_row(p, ta), rd_row(p + 2 * RS, tb);                 // dA, dB
+            if (heavy) rd_row(p + 1 * RS, ta, ra), rd_row(p + 3 * RS, tb, rb);  // d2, d4
+            else rd_row(p, ta, ra), rd_row(p + 2 * RS, tb, rb);                 // dA, dB
         } else if (piece == 1) {
+            take_row(ta, ra), take_row(tb, rb);
             if (heavy) {
 #pragma unroll
                 for (int c = 0; c < 6; ++c) tlo[c] = __builtin_fmaf(al, ta[c], tb[c]);  // X
-                rd_row(p, ta), rd_row(p + 2 * RS, tb);                                    // d1, d3
+                rd_row(p, ta, ra), rd_row(p + 2 * RS, tb, rb);                            // d1, d3
             } else {
 #pragma unroll
                 for (int c = 0; c < 6; ++c) tlo[c] = __builtin_fmaf(4.f, ta[c], -5.f * tb[c]);  // P
-                rd_row(p + 4 * RS, ta);                                                        // dC
+                rd_row(p + 4 * RS, ta, ra);                                                    // dC
             }
         } else if (piece == 2) {
+            take_row(ta, ra);
+            if (heavy) take_row(tb, rb);
             if (heavy) {
 #pragma unroll
                 for (int c = 0; c < 6; ++c) {
@@ -394,10 +461,10 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     }
     dma_u(0, 0);
     if (SPEC != 2) {
-        dma_raw(0, 0 * R_BYTES);
-        dma_raw(1, 1 * R_BYTES);
-        dma_raw(2, 2 * R_BYTES);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");  // U(0), positions 0 and 1 have landed
+        dma_raw_fill(0, 0 * R_BYTES);
+        dma_raw_fill(1, 1 * R_BYTES);
+        dma_raw_fill(2, 2 * R_BYTES);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR) : "memory");  // U(0), positions 0 and 1 have landed
         __syncthreads();  // an LDS-DMA is ordered for a ds_read only by the issuer's vmcnt FOLLOWED by a barrier the reader has passed
     } else {
         int goff[NL];
@@ -458,7 +525,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                 int goff[NL];
                 if (cc + 3 == nchunks) omaskB = write_table(vB);
 #pragma unroll
-                for (int i = 0; i < NL; ++i) goff[i] = gtab[i * NT + tid];
+                for (int i = 0; i < NL; ++i) goff[i] = i < NR ? gtab[i * NT + tid] : 0;
                 float(&rin_s)[NL] = PAR ? rinB : rinA;      // SPEC 2: holds position c+2, staged by this chunk
                 float(&rin_l)[NL] = PAR ? rinA : rinB;      // SPEC 2: receives position c+3
                 Pro pro;
@@ -471,8 +538,8 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                         oa[(q + 1 + PAR) & 1] = *reinterpret_cast<const floatx4*>(U + (q + 1) * 1024);
                     } else {
                         // (partial patches: a wave wholly outside the image issues no store -- nothing to count on)
-                        if (young) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL + (RAG ? 0 : 16)) : "memory");
-                        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+                        if (young) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR + (RAG ? 0 : 16)) : "memory");
+                        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR) : "memory");
                         young = false;
                         __builtin_amdgcn_sched_barrier(0);
                         SLOT_MARK(8)
@@ -492,8 +559,10 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                     acc[4 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, ZERO ? z4 : acc[4 * q + 2], 0, 0, 0);
                     acc[4 * q + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, ZERO ? z4 : acc[4 * q + 3], 0, 0, 0);
                     if (!ZERO) {  // (chunk 0: U(1) was copied whole before the epilogue / by the fill)
-                        if (q < 3) dma_u_piece(cc + 1, PAR ^ 1, q + 1);
-                        if (q == 3 && !HEAVY) dma_u_piece(cc + 1, PAR ^ 1, 4);
+                        if (!G16) {
+                            if (q < 3) dma_u_piece(cc + 1, PAR ^ 1, q + 1);
+                            if (q == 3 && !HEAVY) dma_u_piece(cc + 1, PAR ^ 1, 4);
+                        }
                     }
                     if (SPEC == 2 && q == 5) {
                         // position c+2 (requested over the previous chunk) has arrived: younger than it are the N_U copies of
@@ -504,17 +573,26 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                     }
                     if (SPEC == 2 && q == 6) stage_act(rin_s, cc + 2, pro, r_a, 2, 4);
                     if (SPEC == 2 && q == 7) stage_act(rin_s, cc + 2, pro, r_a, 4, 6);
-                    // position c+3, behind the last piece of U(c+1): the counted wait at the barrier leaves exactly these six in flight
+                    // position c+3, behind the last piece of U(c+1): the counted wait at the barrier leaves exactly these NR in flight
                     auto req = [&](int i) {
                         if (SPEC == 2) ld_raw(rin_l, cc + 3, i, goff[i]);
                         else dma_raw_piece(cc + 3, r_x, i, goff[i]);
                     };
-                    if (HEAVY && q == 3) req(0);
-                    if (!HEAVY && q == 4) req(0);
-                    if (q == 4) req(1);
-                    if (q == 5) req(2);
-                    if (q == 6) req(3);
-                    if (q == 7) req(4), req(5);
+                    if (G16) {  // one piece per quad: weight pieces 1.. of U(c+1) from quad 0, the requests behind the last of them
+                        static_assert(!G16 || N_U - 1 + NR <= 8, "a piece at quad 8 would lie behind the counted wait");
+                        if (q < N_U - 1) {
+                            if (!ZERO) dma_u_piece(cc + 1, PAR ^ 1, q + 1);  // (chunk 0: U(1) was copied whole)
+                        } else if (q < N_U - 1 + NR) {
+                            req(q - (N_U - 1));
+                        }
+                    } else {
+                        if (HEAVY && q == 3) req(0);
+                        if (!HEAVY && q == 4) req(0);
+                        if (q == 4) req(1);
+                        if (q == 5) req(2);
+                        if (q == 6) req(3);
+                        if (q == 7) req(4), req(5);
+                    }
                     if (q < 5) tr_piece(q, r_t, PAR ^ 1);
                     __builtin_amdgcn_sched_barrier(0);
                     if (q < 8) { SLOT_MARK(q) }
@@ -679,19 +757,32 @@ template <int MODE, int SPEC, bool RAG>
 __global__ __launch_bounds__(NT) void conv_wino4_kernel(const ConvArgs a, const Geo4 g TRACE_PARAM) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef IDIFF_WINO_TRACE
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<MODE, SPEC, RAG, true>(a, g, smem, trace);
-    else conv_wino4_body<MODE, SPEC, RAG, false>(a, g, smem, trace);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<MODE, SPEC, RAG, true, false>(a, g, smem, trace);
+    else conv_wino4_body<MODE, SPEC, RAG, false, false>(a, g, smem, trace);
 #else
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<MODE, SPEC, RAG, true>(a, g, smem);
-    else conv_wino4_body<MODE, SPEC, RAG, false>(a, g, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<MODE, SPEC, RAG, true, false>(a, g, smem);
+    else conv_wino4_body<MODE, SPEC, RAG, false, false>(a, g, smem);
 #endif
 }
 
-template <int MODE, int SPEC, bool RAG>
-int launch_rag(const ConvArgs& a, hipStream_t st) {
+// the same kernel with the 16-byte gather (normal mode, SPEC 1 / 3)
+template <int SPEC, bool RAG>
+__global__ __launch_bounds__(NT) void conv_wino4_g16_kernel(const ConvArgs a, const Geo4 g TRACE_PARAM) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+#ifdef IDIFF_WINO_TRACE
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<IDIFF_CONV_NORMAL, SPEC, RAG, true, true>(a, g, smem, trace);
+    else conv_wino4_body<IDIFF_CONV_NORMAL, SPEC, RAG, false, true>(a, g, smem, trace);
+#else
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) conv_wino4_body<IDIFF_CONV_NORMAL, SPEC, RAG, true, true>(a, g, smem);
+    else conv_wino4_body<IDIFF_CONV_NORMAL, SPEC, RAG, false, true>(a, g, smem);
+#endif
+}
+
+template <auto KERN>
+int launch_items(const ConvArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)3 * R_FLOATS + 2 * V_FLOATS + 2 * U_FLOATS + 2 * 256 + NL * NT) * sizeof(float);  // 158 KB
     static idiff_dyn_lds_cache lds_cache;
-    auto kern = conv_wino4_kernel<MODE, SPEC, RAG>;
+    auto kern = KERN;
     if (const int rc = idiff_dyn_lds(lds_cache, kern, lds, "conv2d(winograd4)")) return rc;
     int num_cu = 0;
     if (!idiff_num_cu(&num_cu)) IDIFF_FAIL(IDIFF_E_HIP, "conv2d(winograd4): cannot query the CU count");
@@ -727,6 +818,20 @@ int launch_rag(const ConvArgs& a, hipStream_t st) {
 #endif
     IDIFF_CHECK_LAUNCH("conv2d_fwd(winograd4)");
     return IDIFF_OK;
+}
+
+// Which gather serves the call -- never which kernel family (conv_wino4_items) nor any bit of the result.  The 16-byte pieces need
+// every piece aligned: 16-byte aligned sources, batch strides and rows of whole float4 (then so are the channel planes).  A source
+// slice that starts 4, 8 or 12 bytes past such a boundary, the prologue form (its register path touches every element anyway) and the
+// upsample (a replicated source is no contiguous piece) keep the dword gather.
+template <int MODE, int SPEC, bool RAG>
+int launch_rag(const ConvArgs& a, hipStream_t st) {
+    if constexpr (MODE == IDIFF_CONV_NORMAL && SPEC != 2) {
+        const bool al0 = !(reinterpret_cast<uintptr_t>(a.src0) & 15) && !(a.bs0 & 3) && !(a.Win & 3);
+        const bool al1 = SPEC != 3 || (!(reinterpret_cast<uintptr_t>(a.src1) & 15) && !(a.bs1 & 3));
+        if (al0 && al1) return launch_items<conv_wino4_g16_kernel<SPEC, RAG>>(a, st);
+    }
+    return launch_items<conv_wino4_kernel<MODE, SPEC, RAG>>(a, st);
 }
 
 // U = G g G^T for one (co, ci) (g6 of wino_common.h), stored by pos()

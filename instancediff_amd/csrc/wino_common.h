@@ -129,6 +129,31 @@ __device__ __forceinline__ void gather_decode(const int& tid, unsigned& om, cons
     }
 }
 
+// The same table in 16-byte pieces (normal mode, Win % 4 == 0, x0 % 4 == 0, 16-byte aligned sources and batch strides of whole
+// float4): R is counted in float4 slots -- channel stride PSP4 (PS4 used), RS4 slots per row -- and its column origin lies three floats
+// to the left: row float 3 + c holds patch column c, so that slot j of a row is the ALIGNED global piece ox = x0 - 4 + 4j .. x0 - 1 + 4j,
+// wholly inside the image or wholly outside (Wout % 4 == 0).  Thread `tid` stages slots e0 + i*ES, i < NR (the kernel deals whole
+// wave-instructions of 64 slots to its waves: e0 and NR are the caller's); gtab[i * NT + tid] and the mask (bit i: the thread's slot i
+// is padding / outside) as above.
+template <int NT, int NR, int ES, int PSP4, int PS4, int RS4, typename Args>
+__device__ __forceinline__ void gather_decode16(const int& tid, const int& e0, unsigned& om, const int& y0, const int& x0, const Args& a, int* const& gtab, const int& HWin) {
+    int t = e0;
+    asm volatile("" : "+v"(t));  // (as above)
+    om = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int e = t + i * ES;
+        const int ci = e / PSP4;
+        const int rem = e - ci * PSP4;
+        const int r = rem / RS4;
+        const int j = rem - r * RS4;
+        const int oy = y0 - 1 + r, ox4 = x0 - 4 + 4 * j;  // the row and the first column of the piece
+        const bool in = rem < PS4 && (unsigned)oy < (unsigned)a.Hout && (unsigned)ox4 < (unsigned)a.Wout;
+        gtab[i * NT + tid] = in ? (ci * HWin + oy * a.Win + ox4) * 4 : -1;
+        om |= (in ? 0u : 1u) << i;
+    }
+}
+
 // ---- the 3x3 weight as the packers read it --------------------------------------------------------------------------------------------
 // taps of (co, ci) of the conv the kernel runs: w[co][ci] as stored, or -- transpose: the input-gradient conv -- w[ci][co] rotated by 180
 // degrees (Cin = the stored tensor's second dimension)
