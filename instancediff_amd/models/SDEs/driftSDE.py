@@ -38,6 +38,11 @@ Credible intervals (`interval: L`): with it reverse_ddpm_ensemble
 members that bracket the central level-L interval and the median (one launch, values selected and never rounded) into
 self.last_order_stats.  order_stat_indices states which order statistics those are and the coverage they nominally give.
 
+Calibrating those intervals: with few members that nominal coverage lies below L.  conformal_scale finds, from per-image
+counts of held-out images over calibration_grid's table of scale factors, the factor by which the interval must be widened about the
+median (conformal risk control); its docstring states what the factor guarantees.  Both are pure host functions; the device side that
+produces the counts and applies the factor is not part of the package yet (DESIGN.md §3 says why).
+
 Graph reuse (`reuse_graph: true`): with it the sde keeps the captured step graph, the buffers it is baked on and the cache
 values it reads in a Session per configuration, and a later image of the same shape only refills the buffers (one ops.chain_begin
 launch) and replays.  The bits are those of the per-call path; what changes is who owns the graph's memory: the sde, until
@@ -189,6 +194,74 @@ def ensemble_score_summary(sums, counts, S):
     return dict(N=N, CRPS=tot[0] / N, SKILL=skill, SPREAD=spread, SSR=spread / skill if S > 1 and skill > 0 else nan,
                 RANK_DEV=sum(abs(h / N - 1.0 / (S + 1)) for h in hist), OUTLIERS=(hist[0] + hist[S]) / N, OUTLIERS_nominal=2.0 / (S + 1),
                 hist=hist, invalid=invalid)
+
+
+def calibration_grid(lam_max=8.0, G=513):
+    """The table of scale factors a calibration searches: lam_g = g * lam_max / (G - 1), g = 0 .. G - 1, computed in double and rounded
+    to float32, as a list of G floats (each a float32 value).  2 <= G <= 1024, lam_max finite and > 0; refused if the rounded table is
+    not strictly ascending (a lam_max so small that neighbours collapse)."""
+    if not _is_int(G) or not 2 <= G <= 1024:
+        raise ValueError(f"calibration_grid: G must be an int in [2, 1024], got {G!r}")
+    if isinstance(lam_max, bool) or not isinstance(lam_max, (int, float)) or not (math.isfinite(lam_max) and lam_max > 0):
+        raise ValueError(f"calibration_grid: lam_max must be a finite number > 0, got {lam_max!r}")
+    table = torch.tensor([g * float(lam_max) / (G - 1) for g in range(G)], dtype=torch.float64).to(torch.float32)
+    if not bool(torch.isfinite(table).all()) or not bool((table[1:] > table[:-1]).all()):
+        raise ValueError(f"calibration_grid: {G} points up to lam_max = {lam_max!r} are not strictly ascending in float32")
+    return [float(v) for v in table]
+
+
+def conformal_scale(counts, alpha, lams):
+    """The calibrated scale factor from the counts of N held-out images (conformal risk control), on the host, in exact rational
+    arithmetic (alpha = Fraction(str(alpha)), as order_stat_indices reads its level).
+        counts [N][G + 2]   one row per image, in any order: bin g < G = the pixels whose target first lies inside the interval scaled
+                            about the median by lams[g] (lo_out = c - lam*(c - lo), hi_out = c + lam*(hi - c)), bin G = the pixels no
+                            entry covers, bin G + 1 = the invalid pixels (a NaN, or not lo <= c <= hi)
+        n_i    = sum(counts[i][:G + 1])                    the image's valid pixels; a row with n_i = 0 is refused
+        L_i(g) = 1 - sum(counts[i][:g + 1]) / n_i          the share of the image's valid pixels outside the interval scaled by lams[g]
+        g^     = the smallest g with (sum_i L_i(g) + 1) / (N + 1) <= alpha ;  lam^ = lams[g^]
+    -> dict(lam, g, alpha, N, bound, risk, reached, invalid): bound is the left side at g^ (at the last g when no g qualifies), risk
+    the list of the N-image mean loss per g, invalid the pooled invalid pixels.  If no g of the table qualifies, reached is False and lam
+    and g are None: the table ends too early (a larger lam_max).  N + 1 < 1 / alpha makes the bound unreachable at any lam, since
+    the left side is at least 1 / (N + 1): that raises a ValueError naming the least N.
+    Guarantee: if the calibration images and a new image are exchangeable, and since the loss lies in [0, 1] and does not increase with
+    lam, the EXPECTED share of the new image's pixels outside its interval scaled by lam^ is at most alpha.  That is a statement about
+    the image-level risk in expectation over the draw of the calibration set and the new image.  It is not per-pixel coverage, and it
+    is not a bound that holds for each image."""
+    lams = [float(v) for v in torch.as_tensor(lams).detach().cpu().reshape(-1).tolist()]
+    G = len(lams)
+    if G < 1:
+        raise ValueError("conformal_scale: the table is empty")
+    rows = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, G + 2).tolist()
+    N = len(rows)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, str, fractions.Fraction)):
+        raise ValueError(f"conformal_scale: alpha must be a number in (0, 1), got {alpha!r}")
+    a = fractions.Fraction(str(alpha))
+    if not 0 < a < 1:
+        raise ValueError(f"conformal_scale: alpha must lie in (0, 1), got {alpha!r}")
+    if N < 1:
+        raise ValueError("conformal_scale: no calibration images")
+    if any(c < 0 for r in rows for c in r):
+        raise ValueError("conformal_scale: counts must be >= 0")
+    n = [sum(r[:G + 1]) for r in rows]
+    if any(v == 0 for v in n):
+        raise ValueError(f"conformal_scale: image(s) {[i for i, v in enumerate(n) if v == 0]} have no valid pixel")
+    if (N + 1) * a < 1:
+        raise ValueError(f"conformal_scale: N = {N} calibration images cannot reach alpha = {alpha}: the bound is at least 1 / (N + 1); "
+                         f"alpha = {alpha} needs at least N = {math.ceil(1 / a) - 1}")
+    cum = [0] * N
+    risk, found, bound = [], None, None
+    for g in range(G):
+        loss = fractions.Fraction(0)
+        for i in range(N):
+            cum[i] += rows[i][g]
+            loss += 1 - fractions.Fraction(cum[i], n[i])
+        risk.append(float(loss / N))
+        if found is None:
+            bound = (loss + 1) / (N + 1)
+            if bound <= a:
+                found = g
+    return dict(lam=None if found is None else lams[found], g=found, alpha=alpha, N=N, bound=float(bound), risk=risk,
+                reached=found is not None, invalid=sum(r[G + 1] for r in rows))
 
 
 def _max_batch(rows):
