@@ -570,6 +570,22 @@ int64_t idiff_interval_coverage_ws_ints(int B, int64_t n_s);
 int idiff_ensemble_scores(const float* x, const float* target, float* crps_map, double* sums, int32_t* counts, void* ws, int B, int S,
                           int64_t n_s, idiff_stream_t stream);
 int64_t idiff_ensemble_scores_ws_bytes(int B, int S);
+/* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
+ * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
+ * the flips applied after the transposition:
+ *   y1 = bit1 ? H-1-y : y ;  x1 = bit2 ? W-1-x : x ;  out[r,c,y,x] = bit0 ? src[c,x1,y1] : src[c,y1,x1]
+ * (in torch terms: x.transpose(-1,-2) if bit 0, then .flip(-2) if bit 1, then .flip(-1) if bit 2).  The up to 8 codes travel by value, 3
+ * bits each from bit 0 up; there is no device table.  A code without bit 0 is its own inverse; the inverse of a code with bit 0 has
+ * bits 1 and 2 swapped.  The host computes inverses: the kernel has no inverse mode.
+ * A pure permutation of 32-bit words: bit-identical to the expression above, signed zeros and NaN payloads included.
+ * One launch, grid = (64x64 output tiles of a plane, C, R), 256 threads: a non-transposing row moves 16-byte pieces from the mirrored
+ * position (words reversed under bit 2) without LDS; a transposing row stages its tile in LDS at a pitch of 65 dwords, 16-byte loads along
+ * the input's W and 16-byte stores along the output's W.  Offsets are 64-bit.
+ * Required: 1 <= period <= 8, S >= 1, in_rep >= 1, R >= 1, R % in_rep == 0, C >= 1, H >= 1, W % 4 == 0, H == W if any of the `period` codes has
+ * bit 0 set, R <= 65535 and C <= 65535 (grid axes), in and out 16-byte aligned and not overlapping.  A refused call (IDIFF_E_BADARG)
+ * launches nothing and leaves every buffer as it was. */
+int idiff_dihedral_rows(const float* in, float* out, int R, int C, int H, int W, int in_rep, int S, int period, uint32_t codes,
+                        idiff_stream_t stream);
 /* ---- tiled sampling (driftSDE tile / tile_overlap) ----
  * The chain's state is one full-resolution image [B][C][H][W]; the nets see it as a batch of ny*nx windows of Ph x Pw per image, window
  * row ((b*ny + iy)*nx + ix), each [C][Ph][Pw] contiguous.  W, Pw and the W origins are multiples of 4; all operands 16-byte aligned.

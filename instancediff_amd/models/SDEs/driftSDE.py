@@ -25,6 +25,10 @@ Posterior ensembles (`num_samples: S`): reverse_ddpm_ensemble dra
 reduces them on the device to a per-pixel mean and standard deviation.  Each row is a *member* whose noise comes from a Philox stream
 of its own, a function of (seed, member id, draw index) only, so a member's image does not depend on the batch it was computed in.
 
+Geometric self-ensembles (`self_ensemble: flips | dihedral`): with it the S members of reverse_ddpm_ensemble also differ in
+orientation -- member s runs on the input flipped / transposed by code self_ensemble_codes(kind)[s % len(codes)] and is turned back before
+the reduction: one permutation launch before the chain and one after it, no extra network cost.
+
 Tiled sampling (`tile` / `tile_overlap`): an image larger than the window the nets are built for runs as a batch of
 overlapping windows.  The state stays ONE full-resolution image: every step blends the windows' two predictions into full-image R_hat and
 eps_hat, updates and draws the noise once per pixel on the full image (the plain chain's Philox counters, whatever the tiling), and cuts the
@@ -264,6 +268,43 @@ def conformal_scale(counts, alpha, lams):
                 reached=found is not None, invalid=sum(r[G + 1] for r in rows))
 
 
+SELF_ENSEMBLES = ("flips", "dihedral")
+# identity, flip W, flip H, half turn, then the same four after a transposition (bit 0 = transpose, bit 1 = flip H, bit 2 = flip W)
+_DIHEDRAL_CODES = (0, 4, 2, 6, 1, 5, 3, 7)
+
+
+def _self_ensemble(value):
+    """the self_ensemble option: None (off), "flips" or "dihedral"; everything else -- bools, ints and other strings included -- is
+    refused like solver_order's"""
+    if value is None:
+        return None
+    if not isinstance(value, str) or value not in SELF_ENSEMBLES:
+        raise ValueError(f"driftSDE: self_ensemble must be 'flips' or 'dihedral' (or None: off), got {value!r}")
+    return value
+
+
+def self_ensemble_codes(kind):
+    """The orientation codes of a geometric self-ensemble, in member order: member s of an input runs under code codes[s % len(codes)].
+    A code is 3 bits (include/idiff.h, idiff_dihedral_rows): bit 0 = transpose, bit 1 = flip H, bit 2 = flip W, the flips applied after
+    the transposition.  "dihedral": [0, 4, 2, 6, 1, 5, 3, 7] -- identity, flip W, flip H, half turn, then those four after a
+    transposition: the eight symmetries of the square.  "flips": the first four, which any H x W takes.  Code 0 comes first, so the
+    members with s % len(codes) == 0 are the members of the option-off ensemble, and member s has the same code under both kinds while
+    s % 8 < 4."""
+    kind = _self_ensemble(kind)
+    if kind is None:
+        raise ValueError("self_ensemble_codes: kind must be 'flips' or 'dihedral'")
+    return list(_DIHEDRAL_CODES[:4] if kind == "flips" else _DIHEDRAL_CODES)
+
+
+def inverse_code(k):
+    """the code that undoes code k: k itself without the transposition (flips are involutions that commute), and with it k with the two
+    flip bits swapped (a flip of H before a transposition is a flip of W after it)"""
+    if not _is_int(k) or not 0 <= k < 8:
+        raise ValueError(f"inverse_code: a code is an int in [0, 8), got {k!r}")
+    k = int(k)
+    return k if not k & 1 else 1 | ((k & 2) << 1) | ((k & 4) >> 1)
+
+
 def _max_batch(rows):
     if not _is_int(rows) or rows < 1:
         raise ValueError(f"driftSDE: max_batch must be an int >= 1, got {rows!r}")
@@ -484,7 +525,7 @@ def session_key(sde, kind, rows, chw, ctx_shape, sched, order, T_stop, text_enco
 class driftSDE:
     def __init__(self, nets=None, T=100, max_sigma=0.4, drift_schedule="sigmoid", noise_schedule="sigmoid", eta=1.0, device=None,
                  sample_T=None, sample_timesteps=None, solver_order=None, num_samples=None, max_batch=16, tile=None, tile_overlap=None,
-                 interval=None, reuse_graph=None, tiled_ensemble=None, max_chain_rows=128, **_ignored):
+                 interval=None, reuse_graph=None, tiled_ensemble=None, max_chain_rows=128, self_ensemble=None, **_ignored):
         self.T = int(T)
         self.max_sigma = float(max_sigma)
         self.eta = float(eta)
@@ -522,6 +563,14 @@ class driftSDE:
         self._sessions = collections.OrderedDict()  # session_key -> Session, least recently used first
         self.last_session = None  # None: the per-call path ran; 'captured' / 'replayed': a session was built / reused by the last call
         self.reuse_graph = _reuse_graph(reuse_graph)
+        self.last_member_ops = None
+        self.self_ensemble = _self_ensemble(self_ensemble)
+
+    def set_self_ensemble(self, kind=None):
+        """"flips" / "dihedral": the members of reverse_ddpm_ensemble run on flipped / transposed copies of the input, member s under
+        self_ensemble_codes(kind)[s % len(codes)], and are turned back before they are reduced.  None: off.  Only
+        reverse_ddpm_ensemble reads it; with num_samples = 1 it does nothing."""
+        self.self_ensemble = _self_ensemble(kind)
 
     def set_reuse_graph(self, flag=None):
         """True: reverse_ddpm / reverse_ddpm_ensemble keep their captured step graph in a Session of the sde and replay it for every
@@ -1125,9 +1174,31 @@ class driftSDE:
         runs as tiled member chains: the rows start at full resolution (ops.ensemble_init), are grouped in order by chain_groups(B*S,
         ny*nx, max_chain_rows), and each group is one TiledStepper over its rows.  A member's noise is the untiled chain's, so neither
         the tiling nor the grouping changes which z a pixel gets.  self.last_tiles: the grid (None on the untiled path); reuse_graph
-        does not apply (a tiled chain captures per call)."""
+        does not apply (a tiled chain captures per call).
+        With `self_ensemble` = "flips" / "dihedral" and S > 1 (cond [B, C, H, W], W a multiple of 4, H == W for "dihedral"), member s
+        runs on the input turned by code self_ensemble_codes(kind)[s % len(codes)]: one ops.dihedral_rows launch writes the B*S turned
+        rows, which run through the row machinery above as B*S inputs of one member each (same ids, names and context -- an embedding has
+        no orientation; a tiled ensemble turns the full-resolution rows, not the windows; a session's chain_begin takes the turned rows
+        with S = 1), and one more launch with the inverse codes turns every member back before samples, mean, std, the order statistics
+        and score_ensemble see it.  Both launches stay outside the captured graphs.  self.last_member_ops: the codes used, int64
+        [B, S]; None with the option off or S = 1, when nothing above changes.  `noises` is injected as is, in the rows' own (turned)
+        frame.  Then:
+          * row (b, s) is bit-equal to a one-member call (num_samples = 1, members = [m(b, s)], option off) on the turned cond[b],
+            turned back;
+          * members with code 0 are bit-equal to the same members with the option off;
+          * a member's image still does not depend on batch, chunking, grouping or graph reuse;
+          * the spread now also holds the nets' orientation dependence: a different ensemble from the option-off one, not a reduced one."""
         S = self.num_samples if num_samples is None else _num_samples(num_samples)
         self._refuse_ensemble_of_tiles(S, self._tile)
+        codes = self_ensemble_codes(self.self_ensemble) if (self.self_ensemble is not None and S > 1) else None
+        if codes is not None:  # refused here, before anything is launched
+            if cond.dim() != 4:
+                raise ValueError(f"reverse_ddpm_ensemble: self_ensemble needs cond as [B, C, H, W], got {tuple(cond.shape)}")
+            if cond.shape[3] % 4:
+                raise ValueError(f"reverse_ddpm_ensemble: self_ensemble needs an image width that is a multiple of 4, got {cond.shape[3]}")
+            if any(k & 1 for k in codes) and cond.shape[2] != cond.shape[3]:
+                raise ValueError(f"reverse_ddpm_ensemble: self_ensemble = {self.self_ensemble!r} transposes and needs a square image, got "
+                                 f"{cond.shape[2]} x {cond.shape[3]} ('flips' takes any H x W)")
         sched, nsteps, order = self._chain_plan(reverse_type, optimize_type, noises, T_stop, who="reverse_ddpm_ensemble")
         cond = cond.contiguous()
         B = cond.shape[0]
@@ -1147,13 +1218,19 @@ class driftSDE:
         ctx_rep = None if image_context is None else image_context.repeat_interleave(S, dim=0)
         self.last_session = None
         self.last_tiles = None
+        self.last_member_ops = None
+        # rows_in / S_in: what the row machinery below expands to the B*S rows -- the B inputs, S members each, or with a self-ensemble the
+        # B*S inputs already turned, one member each
+        rows_in, S_in = cond, S
+        if codes is not None:
+            rows_in, S_in = ops.dihedral_rows(cond, codes, S=S, in_rep=S), 1
         idx = self._session_indices(names_rep, cond, image_context, nsteps) if (noises is None and not tiled) else None
         if tiled:
             # chains of G consecutive full-resolution rows, each one TiledStepper over its G*nwin window rows; a tiled chain always
             # captures per call
             plan = self._tile_plan(cond.shape[2], cond.shape[3], cond.device)
             nwin = plan.ny * plan.nx
-            cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
+            cond_rep, x, xa = ops.ensemble_init(rows_in, S_in, mdev, self.max_sigma, self.seed)
             for r0, r1 in chain_groups(R, nwin, self.max_chain_rows):
                 stepper = driftSDE.TiledStepper(self, x[r0:r1], cond_rep[r0:r1], plan, [n for n in names_rep[r0:r1] for _ in range(nwin)],
                                                 text_encoder, None if ctx_rep is None else ctx_rep[r0:r1].repeat_interleave(nwin, dim=0),
@@ -1167,13 +1244,13 @@ class driftSDE:
             how = []
             for r0 in range(0, R, self.max_batch):
                 r1 = min(r0 + self.max_batch, R)
-                rows, stepper, state = self._session_run("member", cond, idx[r0:r1], text_encoder, None if ctx_rep is None else ctx_rep[r0:r1],
-                                                         sched, nsteps, order, T_stop, r1 - r0, members=ids[r0:r1], S=S, row0=r0)
+                rows, stepper, state = self._session_run("member", rows_in, idx[r0:r1], text_encoder, None if ctx_rep is None else ctx_rep[r0:r1],
+                                                         sched, nsteps, order, T_stop, r1 - r0, members=ids[r0:r1], S=S_in, row0=r0)
                 ops.axpby(rows, rows, 1.0, 0.0, out=x[r0:r1])
                 how.append(state)
             self.last_session = None if None in how else ("captured" if "captured" in how else "replayed")
         else:
-            cond_rep, x, xa = ops.ensemble_init(cond, S, mdev, self.max_sigma, self.seed)
+            cond_rep, x, xa = ops.ensemble_init(rows_in, S_in, mdev, self.max_sigma, self.seed)
             for r0 in range(0, R, self.max_batch):
                 r1 = min(r0 + self.max_batch, R)
                 stepper = driftSDE.Stepper(self, x[r0:r1], cond_rep[r0:r1], names_rep[r0:r1], text_encoder,
@@ -1183,6 +1260,9 @@ class driftSDE:
                 stepper.run(nsteps)
         self._record_run(stepper, nsteps, order)
         self.last_members = torch.tensor(ids, dtype=torch.int64).view(B, S)
+        if codes is not None:  # every member back into the input's frame, outside the captured graphs
+            x = ops.dihedral_rows(x, [inverse_code(k) for k in codes], S=S)
+            self.last_member_ops = torch.tensor([codes[s % len(codes)] for s in range(S)] * B, dtype=torch.int64).view(B, S)
         samples = x.view((B, S) + tuple(cond.shape[1:]))
         mean, std = ops.ensemble_stats(samples)
         self.last_order_stats = None if self.interval is None else self._order_stats(samples, self.interval)

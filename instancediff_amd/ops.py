@@ -957,6 +957,43 @@ def ensemble_scores(x, target, want_map=False):
     return sums, counts, crps_map
 
 
+def dihedral_rows(x, codes, S=None, in_rep=1, out=None):
+    """x [B, C, H, W] -> [B * in_rep, C, H, W]: output row r is input row r // in_rep under the code codes[(r % S) % len(codes)], a flip
+    and / or transposition of its planes (idiff_dihedral_rows).  codes: a host list of 1 to 8 ints in [0, 8): bit 0 = transpose, bit 1 =
+    flip H, bit 2 = flip W, the flips after the transposition -- x.transpose(-1, -2) if bit 0, then .flip(-2) if bit 1, then .flip(-1) if
+    bit 2.  S (None: the number of output rows, so row r simply takes code r % len(codes)) is the period of the member index, as in the
+    B*S rows of an ensemble.  W must be a multiple of 4 and a transposing code needs H == W; out, if given, must not overlap x.  One
+    launch; a pure permutation, bit for bit."""
+    lib = _lib.load()
+    codes = list(codes)
+    if not 1 <= len(codes) <= 8 or any(not isinstance(k, int) or isinstance(k, bool) or not 0 <= k < 8 for k in codes):
+        raise ValueError(f"dihedral_rows: codes must be 1 to 8 ints in [0, 8), got {codes}")
+    if isinstance(in_rep, bool) or not isinstance(in_rep, int) or in_rep < 1:
+        raise ValueError(f"dihedral_rows: in_rep must be an int >= 1, got {in_rep!r}")
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"dihedral_rows: x must be a [B, C, H, W] tensor, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    B, Cc, H, W = x.shape
+    R = B * in_rep
+    S = R if S is None else S
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError(f"dihedral_rows: S must be an int >= 1 (or None: the number of output rows), got {S!r}")
+    if W % 4:
+        raise ValueError(f"dihedral_rows: the image width {W} is not a multiple of 4")
+    if H != W and any(k & 1 for k in codes):
+        raise ValueError(f"dihedral_rows: a transposing code needs a square image, got {H} x {W} with codes {codes}")
+    _c(x, "x")
+    if out is None:
+        out = torch.empty((R, Cc, H, W), device=x.device, dtype=torch.float32)
+    _c(out, "out")
+    if tuple(out.shape) != (R, Cc, H, W):
+        raise _lib.IdiffError(f"dihedral_rows: out must be {(R, Cc, H, W)}, got {tuple(out.shape)}")
+    packed = 0
+    for i, k in enumerate(codes):
+        packed |= k << (3 * i)
+    check(lib.idiff_dihedral_rows(_p(x), _p(out), R, Cc, H, W, in_rep, S, len(codes), packed, _stream()), "dihedral_rows")
+    return out
+
+
 def plane_sum(x):
     """x [B, C, H, W] -> [B, C]: the sum over the pixels of every plane"""
     lib = _lib.load()

@@ -14,6 +14,8 @@ With `--scores` on top of `--num-samples S` the ensemble is verified against the
 pooled scores are printed and the pooled rank histogram goes to `rank_hist.json`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
+With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
+transposed copy of the image and is turned back before the mean, the maps and the scores (a geometric self-ensemble).
 With `--random-init` the checkpoint load
 is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
 """
@@ -65,11 +67,19 @@ def main(argv=None):
     parser.add_argument("--reuse-graph", action="store_true",
                         help="driftSDE reuse_graph: keep the captured step graph and replay it for every later image of the same shape "
                              "(same bits; overrides the YAML)")
+    parser.add_argument("--self-ensemble", type=str, default=None, choices=("flips", "dihedral"),
+                        help="driftSDE self_ensemble: member s of an ensemble runs on the image flipped (flips: any H x W) or flipped / "
+                             "transposed (dihedral: square images) and is turned back before the reduction (needs num_samples > 1; "
+                             "overrides the YAML)")
     args = parser.parse_args(argv)
     if args.tile is not None and len(args.tile) > 2:
         parser.error("--tile takes one size P or two, Ph Pw")
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
+    if args.self_ensemble is not None:  # refused before the model is built: the option only turns the members of an ensemble
+        num = args.num_samples if args.num_samples is not None else opt['sdes'][opt['test']['which_sde']].get('num_samples')
+        if not isinstance(num, int) or num <= 1:
+            parser.error("--self-ensemble turns the members of an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
     rank, world, local = parallel.init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local if world > 1 else opt['gpu_ids'][0])
@@ -100,6 +110,8 @@ def main(argv=None):
         sde_opt['max_chain_rows'] = args.max_chain_rows
     if args.reuse_graph:
         sde_opt['reuse_graph'] = True
+    if args.self_ensemble is not None:
+        sde_opt['self_ensemble'] = args.self_ensemble
     sde = create_sde(model.get_nets(use_ema=test_opt['use_ema']), sde_opt)
     sde.set_gpu(model.device)
     model.set_sde(sde)
@@ -107,6 +119,7 @@ def main(argv=None):
     S = getattr(sde, 'num_samples', 1)
     if args.scores and S <= 1:
         parser.error("--scores verifies an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
+    kind = getattr(sde, 'self_ensemble', None) if S > 1 else None
     result_root = os.path.join(test_opt['result_root'], opt['name'])
     results = OrderedDict((a, {'num': 0, 'RMSE': [], 'SSIM': [], 'PSNR': []}) for a in opt['artifact_type'])
     if S > 1:
@@ -195,6 +208,7 @@ def main(argv=None):
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
               + (f", {S} samples per image" if S > 1 else "")
+              + ("" if kind is None else f", self-ensemble {kind}")
               + ("" if level is None else f", interval {level} (nominal {sde.last_order_stats['nominal']})")
               + ("" if getattr(sde, 'last_tiles', None) is None else ", {}x{} windows of {}x{}".format(*sde.last_tiles))
               + (f", graph reused for {n_replayed} of {len(times)} images" if getattr(sde, 'reuse_graph', False) else ""))
