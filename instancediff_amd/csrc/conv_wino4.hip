@@ -22,6 +22,8 @@
 //   Same fused gather (virtual concat, nearest x2 upsample, GroupNorm/FiLM affine + SiLU prologue) and the same epilogue
 //   contract (bias, residual, per-(b,c) vector, "+silu(a*aux+b)", GroupNorm partials per 8x32 patch) as conv_igemm.hip
 //   and conv_wino.hip; the three kernels are interchangeable behind idiff_conv2d_fwd.
+//
+//   Upsample mode multiplies 25 of the 36 positions: the other 11 are exactly +0 for a nearest x2 source (pos_live, wino_common.h).
 #include "conv_args.h"
 #include "wino_common.h"
 
@@ -45,6 +47,22 @@ constexpr int V_FLOATS = 9 * 2 * 64 * 4;   // 4608
 constexpr int U_FLOATS = 9 * 4 * 64 * 4;   // 9216
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
+
+// The main loop's plan of a chunk's nine position quads, from quad_live (wino_common.h).  chunk_live: four bits per quad, bit c = the
+// MFMA of component c is issued.  A quad without a live component (upsample: quad 3) reads no operands and its predecessor requests the
+// next live quad's instead.  chunk_sets: bit q = parity of the live quads before q -- the operand register set quad q alternates onto.
+template <bool UPSAMPLED>
+constexpr unsigned long long chunk_live() {
+    unsigned long long m = 0;
+    for (int q = 0; q < 9; ++q) m |= (unsigned long long)quad_live<UPSAMPLED>(q) << (4 * q);
+    return m;
+}
+template <bool UPSAMPLED>
+constexpr unsigned chunk_sets() {  // bits 0..8; bit 9 = parity of a chunk's live quads
+    unsigned m = 0, n = 0;
+    for (int q = 0; q < 9; ++q) m |= (n & 1u) << q, n += quad_live<UPSAMPLED>(q) != 0;
+    return m | (n & 1u) << 9;
+}
 
 struct Geo4 {
     int np;        // 16x32 patches per sample
@@ -110,6 +128,11 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     constexpr int HU = G16 ? 5 : 4, HR = 3;
     constexpr int N_U = HEAVY ? HU : 9 - HU;
     constexpr int NR = G16 ? (HEAVY ? HR : 3 - HR) : NL;
+    // Upsample mode: the 11 Winograd positions with u == 2 or v == 2 are exactly +0 in every tile (pos_live in wino_common.h).  Their
+    // MFMAs, accumulators, the operand reads of quad 3, Winograd row 2 of the input transform and column 2 of every bt6 are left out, and
+    // the output transform takes literal +0 in their place: 25 products per tile and channel pair, the bits of all 36.  The nine quad
+    // slots of a chunk, the staging slices, the LDS-DMA dealing and the weight copy (quad 3's pieces included) are what they were.
+    constexpr bool UPS = MODE == IDIFF_CONV_UPSAMPLE2;
     float* const Rb = smem;                   // [3][R_FLOATS]
     float* const Vb = smem + 3 * R_FLOATS;    // [2][V_FLOATS]
     float* const Ub = Vb + 2 * V_FLOATS;      // [2][U_FLOATS]
@@ -400,11 +423,16 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
             take_row(ta, ra);
             if (heavy) take_row(tb, rb);
             if (heavy) {
+                if (UPS && !trole) {  // (uniform) Winograd row 2 = X - Y is exactly +0 (pos_live): row 1 alone is computed and written
 #pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    const float X = tlo[c], Y = __builtin_fmaf(al, ta[c], tb[c]);
-                    tlo[c] = __builtin_fmaf(be, Y, X);
-                    thi[c] = __builtin_fmaf(-be, Y, X);
+                    for (int c = 0; c < 6; ++c) tlo[c] = __builtin_fmaf(be, __builtin_fmaf(al, ta[c], tb[c]), tlo[c]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) {
+                        const float X = tlo[c], Y = __builtin_fmaf(al, ta[c], tb[c]);
+                        tlo[c] = __builtin_fmaf(be, Y, X);
+                        thi[c] = __builtin_fmaf(-be, Y, X);
+                    }
                 }
             } else {
 #pragma unroll
@@ -413,8 +441,9 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
         } else {
             const int which = piece - 3;
             if (which == 1 && !heavy) return;
+            if (UPS && which == 1 && !trole) return;  // (uniform) row 2 of an upsampled source: no MFMA reads it
             float o[6];
-            bt6(which ? thi : tlo, o);
+            bt6<UPS>(which ? thi : tlo, o);
             const int u = ufirst + which;
             float* const V = vwbase + buf * V_FLOATS;
             *reinterpret_cast<floatx4*>(V + PF(u) * 512) = floatx4{o[0], o[1], o[2], o[3]};
@@ -499,7 +528,9 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
     for (int item = first; item < last; item += G) {
         TRACE_MARK(0)
         TRACE_LAP(3)  // "to next item"
-        floatx4 acc[36];  // started from C = 0 by the first chunk's MFMAs (no 144 v_mov per item)
+        // started from C = 0 by the first chunk's MFMAs (no 144 v_mov per item).  Upsample: the 11 dead positions are never written or
+        // read, so they hold no register: 100 accumulator registers of the 144
+        floatx4 acc[36];
         {
             // ONE barrier per chunk.  Chunk c runs its 9 position quads and, one slice per quad:
             //   transform position c+1 (slot r_t) -> V[(c+1)&1];  SPEC 2: activate position c+2 from its registers into slot r_a;
@@ -516,7 +547,13 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                 const float* U = Ub + PAR * U_FLOATS + cb * 256 + opoff;
                 // Operand quads alternate between two register sets; the parity flips from chunk to chunk (9 quads), so quad 8 of
                 // this chunk and quad 0 of the next never share a set: the next chunk's first operands are requested right after
-                // the barrier and arrive while the four MFMAs of this chunk's last quad run.
+                // the barrier and arrive while the four MFMAs of this chunk's last quad run.  (Upsample: the eight LIVE quads
+                // alternate, sets 0 .. 1 in every chunk -- quad 8 on set 1, the next quad 0 on set 0.)
+                constexpr unsigned long long LIVE = chunk_live<UPS>();
+                constexpr unsigned SETS = chunk_sets<UPS>();
+                static_assert((LIVE >> 32) != 0 && (LIVE & 0xf) != 0, "quads 0 and 8 carry the chunk's first and last operand requests");
+                auto qlive = [](int q) { return (unsigned)(LIVE >> (4 * q)) & 0xfu; };
+                auto qset = [](int q, int par) { return (int)(((SETS >> q) ^ ((SETS >> 9) & (unsigned)par)) & 1u); };
                 const float* Vn = Vb + (PAR ^ 1) * V_FLOATS + tblk * 256 + opoff;
                 const float* Un = Ub + (PAR ^ 1) * U_FLOATS + cb * 256 + opoff;
                 // Position c+3 is requested during this chunk, one element per quad: SPEC 1 / 3 by LDS-DMA into the slot freed by the
@@ -533,9 +570,13 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                 SLOT_START
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
+                    const unsigned lm = qlive(q);
                     if (q + 1 < 9) {
-                        ob[(q + 1 + PAR) & 1] = *reinterpret_cast<const floatx4*>(V + (q + 1) * 512);
-                        oa[(q + 1 + PAR) & 1] = *reinterpret_cast<const floatx4*>(U + (q + 1) * 1024);
+                        if (lm) {  // (a dead quad's slot requests nothing: the quad before it has asked for the next live one)
+                            const int nq = qlive(q + 1) ? q + 1 : q + 2;
+                            ob[qset(nq, PAR)] = *reinterpret_cast<const floatx4*>(V + nq * 512);
+                            oa[qset(nq, PAR)] = *reinterpret_cast<const floatx4*>(U + nq * 1024);
+                        }
                     } else {
                         // (partial patches: a wave wholly outside the image issues no store -- nothing to count on)
                         if (young) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NR + (RAG ? 0 : 16)) : "memory");
@@ -549,15 +590,17 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
                         // first piece here and the others over the next chunk's first quads
                         if (cc + 1 == nchunks) dma_u(cc + 2, PAR);
                         else dma_u_piece(cc + 2, PAR, 0);
-                        ob[PAR ^ 1] = *reinterpret_cast<const floatx4*>(Vn);
-                        oa[PAR ^ 1] = *reinterpret_cast<const floatx4*>(Un);
+                        ob[qset(0, PAR ^ 1)] = *reinterpret_cast<const floatx4*>(Vn);
+                        oa[qset(0, PAR ^ 1)] = *reinterpret_cast<const floatx4*>(Un);
                     }
-                    const floatx4 bv = ob[(q + PAR) & 1], av = oa[(q + PAR) & 1];
-                    const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
-                    acc[4 * q + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, ZERO ? z4 : acc[4 * q + 0], 0, 0, 0);
-                    acc[4 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, ZERO ? z4 : acc[4 * q + 1], 0, 0, 0);
-                    acc[4 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, ZERO ? z4 : acc[4 * q + 2], 0, 0, 0);
-                    acc[4 * q + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, ZERO ? z4 : acc[4 * q + 3], 0, 0, 0);
+                    if (lm) {
+                        const floatx4 bv = ob[qset(q, PAR)], av = oa[qset(q, PAR)];
+                        const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
+                        if (lm & 1u) acc[4 * q + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, ZERO ? z4 : acc[4 * q + 0], 0, 0, 0);
+                        if (lm & 2u) acc[4 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, ZERO ? z4 : acc[4 * q + 1], 0, 0, 0);
+                        if (lm & 4u) acc[4 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, ZERO ? z4 : acc[4 * q + 2], 0, 0, 0);
+                        if (lm & 8u) acc[4 * q + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, ZERO ? z4 : acc[4 * q + 3], 0, 0, 0);
+                    }
                     if (!ZERO) {  // (chunk 0: U(1) was copied whole before the epilogue / by the fill)
                         if (!G16) {
                             if (q < 3) dma_u_piece(cc + 1, PAR ^ 1, q + 1);
@@ -656,12 +699,16 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
             constexpr int AUX_SC1 = 1 << 4;  // write-through
             // Phase 1: A^T along the Winograd columns v of every row u and channel r -- 144 accumulators shrink to 96 values
             // (the accumulators of a row die as soon as it is done, so the registers hold either form, never both).
+            // Upsample: a dead position (pos_live) has no accumulator; the transforms take the literal +0 it would hold, their adds
+            // as they stand (-0 + 0 is +0: no x + 0 is simplified by hand).  Row u = 2 is +0 throughout, and so are its sums.
             float zz[6][4][4];  // [u][r][dx]
+            auto m = [&](int u, int v, int r) { return pos_live<UPS>(u, v) ? acc[pos(u, v)][r] : 0.f; };
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
+                if (UPS && u == 2) continue;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    at6(acc[pos(u, 0)][r], acc[pos(u, 1)][r], acc[pos(u, 2)][r], acc[pos(u, 3)][r], acc[pos(u, 4)][r], acc[pos(u, 5)][r], zz[u][r]);
+                    at6(m(u, 0, r), m(u, 1, r), m(u, 2, r), m(u, 3, r), m(u, 4, r), m(u, 5, r), zz[u][r]);
                     // pinned here: left alone, the optimiser sinks these sums to their uses in phase 2 and keeps the accumulators
                     // alive until then
                     asm volatile("" : "+v"(zz[u][r][0]), "+v"(zz[u][r][1]), "+v"(zz[u][r][2]), "+v"(zz[u][r][3]));
@@ -691,7 +738,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const Geo4& g
 #pragma unroll
                 for (int x = 0; x < 4; ++x) {
                     float col[4];
-                    at6(zz[0][r][x], zz[1][r][x], zz[2][r][x], zz[3][r][x], zz[4][r][x], zz[5][r][x], col);
+                    at6(zz[0][r][x], zz[1][r][x], UPS ? 0.f : zz[2][r][x], zz[3][r][x], zz[4][r][x], zz[5][r][x], col);
 #pragma unroll
                     for (int dy = 0; dy < 4; ++dy) y[dy][x] = col[dy] + bv;
                 }

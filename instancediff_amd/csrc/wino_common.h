@@ -53,12 +53,38 @@ __host__ __device__ constexpr int PF(int u) { return (3 * u + 1) / 2; }       //
 __host__ __device__ constexpr int PH(int u) { return 1 + 3 * (u / 2); }       // 1, 1, 4, 4, 7, 7
 __host__ __device__ constexpr int pos(int u, int v) { return v < 4 ? 4 * PF(u) + v : 4 * PH(u) + 2 * (u & 1) + (v - 4); }
 
-// one 6-point input transform B^T x
+// Which positions carry anything when the source is a nearest x2 upsample.  The 6x6 input tile of a 4x4 output tile starts at an odd row
+// and column of the x2 grid (oy = y0 - 1 + r with y0 % 4 == 0, source row oy >> 1: gather_decode), so tile rows 1 and 2 are the same
+// low-resolution row bit for bit, and so are rows 3 and 4; Hout and Wout are even, so such a pair lies wholly inside the image or is
+// wholly padding.  The columns behave the same way.  In B^T d B as the kernels compute it, Winograd row 2 is fma(-1, Y, X) with
+// X = fma(-4, d2, d4) and Y = fma(-4, d1, d3) the same bits, and column 2 is p - q of bt6 with p and q the same bits: every position
+// (u, v) with u == 2 or v == 2 is exactly +0 in every tile, 11 of the 36, and its accumulator stays the +0 it starts from
+// (+0 + (+-0) = +0).  A kernel that leaves those products out and hands literal +0 to the output transform returns the bits of one that
+// multiplies all 36 (finite operands: 0 * inf is NaN only where the product is formed).  tests/test_wino_upsample_cpu.py checks the rule
+// by brute force over every tile of padded images, border tiles included: these 11 are always zero and none of the other 25 is.
+template <bool UPSAMPLED>
+__host__ __device__ constexpr bool pos_live(int u, int v) {
+    return !UPSAMPLED || (u != 2 && v != 2);
+}
+// the same per position quad of pos(): bit c = component c of the quad's 16-byte operands is live (normal source: 0xf throughout;
+// upsampled: quads 0, 2, 5, 6, 8 -> {0, 1, 3}, quads 1, 7 -> all four, quad 4 -> {2, 3}, quad 3 -> none)
+template <bool UPSAMPLED>
+__host__ __device__ constexpr unsigned quad_live(int quad) {
+    unsigned m = 0;
+    for (int u = 0; u < 6; ++u)
+        for (int v = 0; v < 6; ++v)
+            if (pos_live<UPSAMPLED>(u, v) && pos(u, v) / 4 == quad) m |= 1u << (pos(u, v) & 3);
+    return m;
+}
+
+// one 6-point input transform B^T x.  UPSAMPLED (pos_live): o[2] is exactly +0 and no reader takes it; it is left holding p, which is
+// at hand, instead of spending the subtraction
+template <bool UPSAMPLED = false>
 __device__ __forceinline__ void bt6(const float (&x)[6], float (&o)[6]) {
     o[0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
     const float p = __builtin_fmaf(-4.f, x[2], x[4]), q = __builtin_fmaf(-4.f, x[1], x[3]);
     o[1] = p + q;
-    o[2] = p - q;
+    o[2] = UPSAMPLED ? p : p - q;
     const float c = x[4] - x[2], e = x[3] - x[1];
     o[3] = __builtin_fmaf(2.f, e, c);
     o[4] = __builtin_fmaf(-2.f, e, c);

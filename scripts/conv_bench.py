@@ -35,6 +35,8 @@ def main():
         ("L3up 576->256 3x3 +stats", 256, 320, 256, 32, 3, 0, True, False),
         ("L2up 416->256 3x3 +stats", 256, 160, 256, 64, 3, 0, True, False),
         ("up 128->64 3x3 upsample", 128, 0, 64, 128, 3, 1, False, False),
+        ("up 256->128 3x3 upsample @128", 256, 0, 128, 64, 3, 1, False, False),
+        ("up 256->256 3x3 upsample @64", 256, 0, 256, 32, 3, 1, False, False),
         ("res 1x1 144->64", 64, 80, 64, 256, 1, 0, False, False),
         ("res 1x1 128->64", 64, 64, 64, 256, 1, 0, False, False),
         ("res 1x1 208->128", 128, 80, 128, 128, 1, 0, False, False),
@@ -54,7 +56,7 @@ def main():
     ]
     cases = []
     if args.only:
-        shapes = [s for s in shapes if args.only in s[0]]
+        shapes = [s for s in shapes if any(o in s[0] for o in args.only.split(","))]  # comma list of substrings
     for name, C0, C1, Co, H, ks, mode, stats, pro in shapes:
         x0 = torch.randn(B, C0, H, H, device=dev)
         x1 = torch.randn(B, C1, H, H, device=dev) if C1 else None
