@@ -570,6 +570,41 @@ int64_t idiff_interval_coverage_ws_ints(int B, int64_t n_s);
 int idiff_ensemble_scores(const float* x, const float* target, float* crps_map, double* sums, int32_t* counts, void* ws, int B, int S,
                           int64_t n_s, idiff_stream_t stream);
 int64_t idiff_ensemble_scores_ws_bytes(int B, int S);
+/* Ensemble member distances: x [B][S][n_s] (the samples of an ensemble), target [B][n_s] or NULL -> per image the matrix of
+ * squared L2 distances between whole images, and two member picks read off it.  Per image there are M = S + (target != NULL) rows
+ * r_0 .. r_{M-1}: the members in index order, then the target.  A pixel is valid iff all M of its values are finite (NaN and +-inf both
+ * make it invalid); an invalid pixel adds to no pair, so every entry of an image's matrix is a distance over the same pixel set.
+ *   d2     float64 [B][M][M]: for i < j, d2[i][j] = d2[j][i] = sum over the valid pixels of d*d, d = (double)r_i - (double)r_j (one fp64
+ *          subtraction; no Gram form: members differ by far less than their magnitude).  The diagonal is exactly +0.0 and the two
+ *          halves carry the same bits.
+ *   counts int32 [B][2] = {valid, invalid}
+ *   pick   int32 [B][2], from the finished matrix:
+ *          pick[b][0], the medoid: the first i (strict <, scanning from 0) that minimises m_i = sum_{j < S, j != i} sqrt(d2[i][j]), the
+ *          correctly rounded fp64 roots added in index order; 0 for S = 1.  (With squared distances the medoid would be the member
+ *          nearest to the mean; with the roots it is not.)
+ *          pick[b][1], the best member: the first i that minimises d2[i][S]; -1 without a target.
+ *          An image with no valid pixel has an all-zero matrix and picks 0.
+ *   ws     idiff_ensemble_distances_ws_bytes(B, S, target != NULL) bytes, 8-byte aligned
+ * Two launches.  The first cuts the matrix into 8 x 8 tiles: one block of 256 threads per (image, one of 64 parts, tile pair ti <= tj),
+ * one float4 per lane and row, grid-stride; a thread holds its tile's 8 + 8 rows and 64 fp64 accumulators in registers (a diagonal tile
+ * its 28 pairs i < j), reads the other rows too for the validity of its pixels (the re-reads across tile pairs come from L2) and folds
+ * its pixels' terms into a pair's accumulator with fma(d, d, acc) in loop order, the four elements of a float4 in index order.  Then
+ * idiff_ensemble_scores' reduction: a fixed xor-shuffle tree per wave (offsets 32, 16, .. 1), the four waves in index order, one fp64
+ * partial per block and pair.  The second launch (one block per image) adds the 64 partials of a pair in index order and makes the
+ * picks.  No atomics: the result of image b does not depend on B and is bit-identical from run to run.
+ * 1 <= S <= 64, n_s % 4 == 0, n_s < 2^31, 1 <= B <= 65535; x / target 16-byte aligned, d2 / ws 8-byte aligned; d2, counts, pick and ws
+ * overlap neither each other nor x or target.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_ensemble_distances(const float* x, const float* target, double* d2, int32_t* counts, int32_t* pick, void* ws, int B, int S,
+                             int64_t n_s, idiff_stream_t stream);
+int64_t idiff_ensemble_distances_ws_bytes(int B, int S, int has_target);
+/* out [B][n_s] <- x[b][k][:] of x [B][S][n_s] with k = pick[b * pick_stride], an int32 table read on the device (no host copy): e.g. a
+ * column of idiff_ensemble_distances' pick with pick_stride = 2.  A pure copy of 32-bit words in 16-byte pieces: signed zeros and NaN
+ * payloads are kept.  If k is outside [0, S) the row is filled with the quiet NaN 0x7fc00000 and nothing of x is read: the table is
+ * caller memory, and an out-of-range index never becomes an address.  One launch, 256 threads, grid-stride, grid = (chunks, B).
+ * 1 <= S <= 64, n_s % 4 == 0, n_s < 2^31, 1 <= B <= 65535, pick_stride >= 1; x / out 16-byte aligned; out overlaps neither x nor the
+ * table.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_ensemble_pick_rows(const float* x, const int32_t* pick, int pick_stride, float* out, int B, int S, int64_t n_s,
+                             idiff_stream_t stream);
 /* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
  * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
  * the flips applied after the transposition:

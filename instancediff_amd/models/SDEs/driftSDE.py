@@ -200,6 +200,68 @@ def ensemble_score_summary(sums, counts, S):
                 hist=hist, invalid=invalid)
 
 
+def ensemble_distance_summary(d2, counts, S, has_target):
+    """The image-level scores of an S-member ensemble from what ops.ensemble_distances returns, on the host in float64:
+        d2 [..., M, M] squared distances between an image's M = S + has_target rows (members, then the target); counts [..., 2] =
+        (valid, invalid) pixels.  Per image, with dist = sqrt(d2), a = sum_i dist[i][S] / S, p = sum_{i != j < S} dist[i][j] (both
+        orders, added in index order) and r = sqrt(valid), so that every distance is a root-mean-square over the valid pixels:
+        ES          (a - p / (2 S^2)) / r      the energy score of the members' empirical distribution, the image-level counterpart
+                                               of the per-pixel CRPS of ensemble_score_summary (same form: the truth sits in no pair)
+        ES_FAIR     (a - p / (2 S (S - 1))) / r   the unbiased ("fair") estimate of the underlying distribution's score; NaN for S = 1
+        DIVERSITY   p / (S (S - 1)) / r        the mean pairwise member distance; NaN for S = 1
+        RMS_member  a / r ;  RMS_best = min_i dist[i][S] / r ;  RMS_medoid = dist[medoid][S] / r
+        medoid      the first i that minimises sum_{j < S, j != i} dist[i][j] (the scan of idiff_ensemble_distances);  best  the first i
+                    that minimises d2[i][S], -1 without a target
+        valid, invalid
+    ES, ES_FAIR, RMS_member, RMS_best and RMS_medoid are NaN without a target; every score is NaN for an image with no valid pixel
+    (medoid 0, best 0 or -1).  Both scores are proper only in expectation over ensembles; ES carries a bias of p / (2 S^2 (S - 1)) / r
+    that rewards a small spread at small S, so to compare ensembles of different spread (or different S) use ES_FAIR.
+    -> dict(key -> the list over images, 'mean' -> dict(key -> the mean of that list over the images): these are per-image scores, so
+    pooling is the mean, unlike the sums of ensemble_score_summary).  Takes tensors, arrays or nested lists."""
+    S = _num_samples(S)
+    M = S + (1 if has_target else 0)
+    d2 = torch.as_tensor(d2, dtype=torch.float64).detach().cpu().reshape(-1, M, M).tolist()
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, 2).tolist()
+    if len(d2) != len(counts):
+        raise ValueError(f"ensemble_distance_summary: {len(d2)} matrices, {len(counts)} rows of counts")
+    nan = float("nan")
+    keys = ("ES", "ES_FAIR", "DIVERSITY", "RMS_member", "RMS_best", "RMS_medoid", "medoid", "best", "valid", "invalid")
+    out = {k: [] for k in keys}
+    for mat, (valid, invalid) in zip(d2, counts):
+        dist = [[math.sqrt(v) for v in row] for row in mat]
+        rows = []
+        for i in range(S):
+            m = 0.0
+            for j in range(S):
+                if j != i:
+                    m += dist[i][j]
+            rows.append(m)
+        medoid = min(range(S), key=lambda i: (rows[i], i))
+        best = min(range(S), key=lambda i: (mat[i][S], i)) if has_target else -1
+        one = dict(ES=nan, ES_FAIR=nan, DIVERSITY=nan, RMS_member=nan, RMS_best=nan, RMS_medoid=nan, medoid=medoid, best=best, valid=valid,
+                   invalid=invalid)
+        if valid > 0:
+            r = math.sqrt(valid)
+            p = 0.0
+            for m in rows:
+                p += m
+            if S > 1:
+                one["DIVERSITY"] = p / (S * (S - 1)) / r
+            if has_target:
+                a = 0.0
+                for i in range(S):
+                    a += dist[i][S]
+                a /= S
+                one["ES"] = (a - p / (2 * S * S)) / r
+                if S > 1:
+                    one["ES_FAIR"] = (a - p / (2 * S * (S - 1))) / r
+                one["RMS_member"], one["RMS_best"], one["RMS_medoid"] = a / r, dist[best][S] / r, dist[medoid][S] / r
+        for k in keys:
+            out[k].append(one[k])
+    out["mean"] = {k: (sum(out[k]) / len(out[k]) if out[k] else nan) for k in keys}
+    return out
+
+
 def calibration_grid(lam_max=8.0, G=513):
     """The table of scale factors a calibration searches: lam_g = g * lam_max / (G - 1), g = 0 .. G - 1, computed in double and rounded
     to float32, as a list of G floats (each a float32 value).  2 <= G <= 1024, lam_max finite and > 0; refused if the rounded table is
@@ -1279,6 +1341,19 @@ class driftSDE:
             raise ValueError(f"score_ensemble: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
                              f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
         return ops.ensemble_scores(samples.contiguous(), target.contiguous(), want_map=want_map)
+
+    @staticmethod
+    def member_distances(samples, target=None):
+        """Image-to-image distances of samples [B, S, ...] (reverse_ddpm_ensemble(..., return_samples=True)), with target [B, ...] as a
+        last row when given -> (d2 float64 [B, M, M], counts int32 [B, 2], pick int32 [B, 2] = medoid, best member) on the device, from
+        one ops.ensemble_distances call (two launches, no host copy); ensemble_distance_summary(d2, counts, S, target is not None)
+        reads ES / ES_FAIR / DIVERSITY off them, ops.ensemble_pick_rows(samples, pick, col) fetches a picked member."""
+        if not torch.is_tensor(samples) or samples.dim() < 3:
+            raise ValueError("member_distances: samples must be a [B, S, ...] tensor (reverse_ddpm_ensemble(..., return_samples=True))")
+        if target is not None and (not torch.is_tensor(target) or tuple(target.shape) != (samples.shape[0],) + tuple(samples.shape[2:])):
+            raise ValueError(f"member_distances: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+        return ops.ensemble_distances(samples.contiguous(), None if target is None else target.contiguous())
 
     @staticmethod
     def _order_stats(samples, level):

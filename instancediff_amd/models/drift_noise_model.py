@@ -288,6 +288,32 @@ class CLIPDriftModel():
             raise ValueError("score_ensemble: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
         return self.sde.score_ensemble(self.samples, self.target, want_map=want_map)
 
+    def member_distances(self, with_target=True):
+        """image-to-image distances of the members test(return_samples=True) left in self.samples, with self.target as a last row when
+        with_target (driftSDE.member_distances) -> (d2 [B, M, M] float64, counts [B, 2], pick [B, 2] = medoid, best member) on the
+        device: two launches.  The picks are kept for pick_member."""
+        if getattr(self, "samples", None) is None:
+            raise ValueError("member_distances: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        d2, counts, pick = self.sde.member_distances(self.samples, self.target if with_target else None)
+        self._member_pick = (self.samples, bool(with_target), pick)
+        return d2, counts, pick
+
+    def pick_member(self, which="medoid"):
+        """one member per image out of self.samples -> [B, ...]: "medoid", the member with the smallest summed distance to the other
+        members (a real draw, and the most central one), or "best", the member nearest to self.target (the oracle pick).  One launch on
+        the picks of the last member_distances() call for these samples; without such a call (for "best": one with the target) it is
+        made first."""
+        if which not in ("medoid", "best"):
+            raise ValueError(f'pick_member: which must be "medoid" or "best", got {which!r}')
+        if getattr(self, "samples", None) is None:
+            raise ValueError("pick_member: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        held = getattr(self, "_member_pick", None)
+        if held is None or held[0] is not self.samples or (which == "best" and not held[1]):
+            self.member_distances(with_target=which == "best")
+            held = self._member_pick
+        from .. import ops
+        return ops.ensemble_pick_rows(self.samples.contiguous(), held[2], 0 if which == "medoid" else 1)
+
     def get_visuals(self):
         return self.visuals
 

@@ -957,6 +957,47 @@ def ensemble_scores(x, target, want_map=False):
     return sums, counts, crps_map
 
 
+def ensemble_distances(x, target=None):
+    """x [B, S, ...] (the samples of an ensemble), target [B, ...] or None -> (d2 float64 [B, M, M], counts int32 [B, 2], pick int32
+    [B, 2]), all on the device, M = S + (target is not None): per image the squared L2 distances between its M rows (the members in
+    index order, then the target) over the pixels at which all M rows are finite; counts = (valid, invalid) pixels; pick = (medoid,
+    best member), the best member -1 without a target.  Two launches, no host copy; include/idiff.h states the arithmetic and the
+    scan order.  models/SDEs/driftSDE.py's ensemble_distance_summary turns d2 and counts into ES / ES_FAIR / DIVERSITY."""
+    lib = _lib.load()
+    _c(x, "x"), _c(target, "target")
+    assert x.dim() >= 3, "ensemble_distances: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    assert target is None or tuple(target.shape) == (B,) + tuple(x.shape[2:]), "ensemble_distances: target is x without the member axis"
+    n_s = x.numel() // (B * S) if B * S else 0
+    M = S + (target is not None)
+    d2 = torch.empty((B, M, M), device=x.device, dtype=torch.float64)
+    counts = torch.empty((B, 2), device=x.device, dtype=torch.int32)
+    pick = torch.empty((B, 2), device=x.device, dtype=torch.int32)
+    ws = torch.empty((max(int(lib.idiff_ensemble_distances_ws_bytes(B, S, int(target is not None))), 8) // 8,), device=x.device,
+                     dtype=torch.float64)
+    check(lib.idiff_ensemble_distances(_p(x), _p(target), C.c_void_p(d2.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                       C.c_void_p(pick.data_ptr()), C.c_void_p(ws.data_ptr()), B, S, n_s, _stream()), "ensemble_distances")
+    return d2, counts, pick
+
+
+def ensemble_pick_rows(x, pick, col):
+    """x [B, S, ...], pick int32 [B, ncol] on the device (ops.ensemble_distances' pick), col a host int -> [B, ...]: row b is member
+    pick[b, col] of image b, read on the device (one launch, no host copy), bit for bit.  An index outside [0, S) -- the best member of
+    a call without a target -- gives a row of NaN."""
+    lib = _lib.load()
+    _c(x, "x"), _c(pick, "pick", torch.int32)
+    assert x.dim() >= 3, "ensemble_pick_rows: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    assert pick.dim() == 2 and pick.shape[0] == B, "ensemble_pick_rows: pick is [B, ncol]"
+    if isinstance(col, bool) or not isinstance(col, int) or not 0 <= col < pick.shape[1]:
+        raise _lib.IdiffError(f"ensemble_pick_rows: col must be an int in [0, {pick.shape[1]}), got {col!r}")
+    n_s = x.numel() // (B * S) if B * S else 0
+    out = torch.empty((B,) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+    check(lib.idiff_ensemble_pick_rows(_p(x), C.c_void_p(pick.data_ptr() + 4 * col), pick.shape[1], _p(out), B, S, n_s, _stream()),
+          "ensemble_pick_rows")
+    return out
+
+
 def dihedral_rows(x, codes, S=None, in_rep=1, out=None):
     """x [B, C, H, W] -> [B * in_rep, C, H, W]: output row r is input row r // in_rep under the code codes[(r % S) % len(codes)], a flip
     and / or transposition of its planes (idiff_dihedral_rows).  codes: a host list of 1 to 8 ints in [0, 8): bit 0 = transpose, bit 1 =

@@ -12,6 +12,9 @@ With `--interval L` on top of that the per-pixel median and the level-L credible
 With `--scores` on top of `--num-samples S` the ensemble is verified against the ground truth on the device: `CRPS`, `SSR` (spread-skill ratio) and
 `RANK_DEV` (the rank histogram's distance from flat) are listed per image, a `<i>_crps_WxHx1.raw` map is written, and per artifact type the
 pooled scores are printed and the pooled rank histogram goes to `rank_hist.json`.
+With `--distances` on top of `--num-samples S` the members are compared as whole images on the device: the energy score `ES`, its fair form
+`ES_FAIR` and the mean pairwise member distance `DIVERSITY` are listed per image with `PSNR_best` (the member nearest to the ground truth) and
+`PSNR_medoid` (the most central member), and the medoid is written as `<i>_medoid_WxHx1.raw`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
@@ -32,7 +35,7 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import ensemble_score_summary
+from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary
 
 
 def main(argv=None):
@@ -55,6 +58,9 @@ def main(argv=None):
     parser.add_argument("--scores", action="store_true",
                         help="ensemble scores against the ground truth (needs num_samples > 1): CRPS / SSR / RANK_DEV per image and a CRPS "
                              "map, the pooled scores and rank_hist.json per artifact type")
+    parser.add_argument("--distances", action="store_true",
+                        help="image-level member distances (needs num_samples > 1): the energy score ES / ES_FAIR, DIVERSITY, PSNR_best and "
+                             "PSNR_medoid per image and the medoid member as a map, the averages per artifact type")
     parser.add_argument("--tile", type=int, nargs="+", default=None, metavar="P",
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
@@ -119,6 +125,8 @@ def main(argv=None):
     S = getattr(sde, 'num_samples', 1)
     if args.scores and S <= 1:
         parser.error("--scores verifies an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
+    if args.distances and S <= 1:
+        parser.error("--distances compares the members of an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
     kind = getattr(sde, 'self_ensemble', None) if S > 1 else None
     result_root = os.path.join(test_opt['result_root'], opt['name'])
     results = OrderedDict((a, {'num': 0, 'RMSE': [], 'SSIM': [], 'PSNR': []}) for a in opt['artifact_type'])
@@ -132,6 +140,9 @@ def main(argv=None):
     if args.scores:
         for r in results.values():
             r['CRPS'], r['SSR'], r['RANK_DEV'], r['scores'] = [], [], [], []
+    if args.distances:
+        for r in results.values():
+            r['ES'], r['ES_FAIR'], r['DIVERSITY'], r['PSNR_best'], r['PSNR_medoid'] = [], [], [], [], []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -188,6 +199,18 @@ def main(argv=None):
                     m = crps_map[0, 0].cpu() * 0.5
                     m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_crps_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
                     extra += f", CRPS={r['CRPS'][-1]}, SSR={r['SSR'][-1]}, RANK_DEV={r['RANK_DEV'][-1]}"
+                if args.distances:  # the distances on RMSE's x/2 + 0.5 scale, like the CRPS; the PSNRs from the picked members themselves
+                    d2, dcounts, _ = model.member_distances()
+                    one = ensemble_distance_summary(d2, dcounts, S, True)
+                    medoid, best = model.pick_member("medoid"), model.pick_member("best")
+                    for tag in ('ES', 'ES_FAIR', 'DIVERSITY'):
+                        r[tag].append(0.5 * one[tag][0])
+                    r['PSNR_best'].append(ops.image_metrics(best[:, 0], model.target[:, 0]).cpu().tolist()[0][1])
+                    r['PSNR_medoid'].append(ops.image_metrics(medoid[:, 0], model.target[:, 0]).cpu().tolist()[0][1])
+                    m = medoid[0, 0].cpu()
+                    m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_medoid_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
+                    extra += (f", ES={r['ES'][-1]}, ES_FAIR={r['ES_FAIR'][-1]}, DIVERSITY={r['DIVERSITY'][-1]}, PSNR_best={r['PSNR_best'][-1]}, "
+                              f"PSNR_medoid={r['PSNR_medoid'][-1]}")
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -195,7 +218,8 @@ def main(argv=None):
     for k, v in results.items():
         if v['num']:
             print(k + "".join(f", AVG {m}: {sum(v[m]) / v['num']}" for m in ('RMSE', 'SSIM', 'PSNR') + (('PSNR_member', 'STD') if S > 1 else ())
-                                  + (('PSNR_median', 'COVER', 'WIDTH') if level is not None else ()) + (('CRPS',) if args.scores else ())))
+                                  + (('PSNR_median', 'COVER', 'WIDTH') if level is not None else ()) + (('CRPS',) if args.scores else ())
+                                  + (('ES', 'ES_FAIR', 'DIVERSITY', 'PSNR_best', 'PSNR_medoid') if args.distances else ())))
             if args.scores:  # the type's record: sums and histograms pooled over its images, not the mean of the per-image ratios
                 pooled = ensemble_score_summary(torch.cat([s for s, _ in v['scores']]), torch.cat([c for _, c in v['scores']]), S)
                 v['pooled'] = pooled
