@@ -605,6 +605,29 @@ int64_t idiff_ensemble_distances_ws_bytes(int B, int S, int has_target);
  * table.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
 int idiff_ensemble_pick_rows(const float* x, const int32_t* pick, int pick_stride, float* out, int B, int S, int64_t n_s,
                              idiff_stream_t stream);
+/* Radial power spectra of image rows: x [R][H][W], sub [R / sub_rep][H][W] or NULL, bins int32 [H][Wh], Wh = W/2 + 1
+ * -> out float64 [R][nb].  Row r is the plane a = x[r], or a = (double)x[r] - (double)sub[r / sub_rep] (one exact fp64 subtraction per
+ * pixel: residual spectra without a temporary).  With X[u,v] = sum_y sum_x a[y,x] exp(-2 pi i (u y / H + v x / W)) and
+ * P[u,v] = |X[u,v]|^2 / (H W) over 0 <= u < H, 0 <= v < Wh,
+ *   out[r][k] = sum over the (u, v) with bins[u][v] == k of w_v P[u,v],   w_v = 1 for v == 0 and for v == W/2 when W is even, else 2
+ * (Hermitian symmetry), so that out is the sum over the full H x W frequency plane and sum_k out[r][k] = sum a^2 (Parseval) when the
+ * table sends every point to a bin.  An entry of bins outside [0, nb) drops its point: entries are compared, never used as addresses.
+ * Arithmetic: fp64 throughout, the pixels widened before any operation.  The twiddle of index j and length N is the entry (j mod N) of
+ * a table (cos, sin)(2 pi m / N) = sincospi(2.0 * m / N), m < N, that the first launch fills; the index is reduced in integers.  A
+ * direct DFT as two GEMMs on v_mfma_f64_16x16x4_f64, the rows pass then the columns pass, one code path for any 1 <= H, W <= 1024.
+ * Three launches (table; one block per strip of 16 -- H > 512: 8 -- columns v and row, which keeps the strip's rows-pass result in LDS
+ * and writes w_v P to ws; one block per 64 bins and row, which adds a bin's points in a fixed order: of every 2048 points of the plane
+ * in index order wave w of 16 takes the w-th 128, and the waves' sums are added in wave order).  No atomics: a row's bits depend on (H, W, bins) and its own pixels only,
+ * not on R, its position among the rows or the run.  A row whose image holds a NaN or +-inf (detected, not propagated) gets the quiet
+ * NaN 0x7ff8000000000000 in all nb bins; other rows are untouched.
+ *   ws  idiff_radial_power_spectrum_ws_bytes(R, H, W) = 16 (W + H) + 8 ceil(R / 2) + 8 R H Wh bytes (the table, a flag per row, the
+ *       weighted power planes), 8-byte aligned; 0 for sizes the call refuses
+ * 1 <= R <= 65535, 1 <= H, W <= 1024, nb >= 1; with sub: sub_rep >= 1 and R % sub_rep == 0 (sub_rep is ignored without it); x, sub and
+ * bins 4-byte aligned (16-byte aligned x / sub with W % 4 == 0 load in 16-byte pieces), out and ws 8-byte aligned.  A refused call
+ * (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_radial_power_spectrum(const float* x, const float* sub, int sub_rep, const int32_t* bins, int nb, double* out, void* ws, int R,
+                                int H, int W, idiff_stream_t stream);
+int64_t idiff_radial_power_spectrum_ws_bytes(int R, int H, int W);
 /* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
  * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
  * the flips applied after the transposition:

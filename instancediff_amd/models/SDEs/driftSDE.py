@@ -200,6 +200,76 @@ def ensemble_score_summary(sums, counts, S):
                 hist=hist, invalid=invalid)
 
 
+def spectrum_summary(spectra, counts, S, L=None):
+    """The scale-by-scale scores of a restoration or an S-member ensemble from what driftSDE.power_spectra returns, on the host in
+    float64.  spectra: a dict of per-bin power sums (ops.radial_power_spectrum) with the keys output, target, residual [..., nb] and
+    for S > 1 also members and member_residuals [..., S, nb]; counts [nb]: ops.radial_bins' points per bin; L = max(H, W), the bins'
+    scale (bin k is k / L cycles per pixel; it may be left out for a square image only, whose counts name it: others are refused).  Rows (images) are
+    pooled first, sums with sums, as in ensemble_score_summary; n rows of a bin hold n * counts[k] points.  -> dict(
+        n                   the rows pooled
+        PSD_output, PSD_target, PSD_residual [nb]   pooled sum / (n counts): the mean power per frequency point of the bin
+        PSD_member, PSD_member_residual [nb]        the same, averaged over the S members (S > 1)
+        RATIO_output [nb]   PSD_output / PSD_target: below 1 where the restoration lacks the truth's power (over-smoothing), above 1
+                            where it adds power;  RATIO_member [nb] the same for the members' mean power
+        HF_RATIO_output, HF_RATIO_member   the same ratios of the power summed over the bins k > L/4 (above half Nyquist)
+        LSD_output, LSD_member             the log-spectral distance sqrt(mean_k (10 log10 ratio_k)^2) in dB over 1 <= k <= L/2, the
+                                           bins with both powers > 0
+        SPREAD_PSD [nb]     S/(S - 1) (mean_s PSD_member_s - PSD_output): the members' variance about their mean, per frequency
+        SKILL_PSD [nb]      PSD_residual: the squared error of the mean, per frequency
+        SSR_k [nb]          sqrt((S + 1)/S SPREAD_PSD / SKILL_PSD), ensemble_score_summary's spread-skill ratio separated per
+                            frequency: 1 at every k for a reliable ensemble, below 1 where it is under-dispersive
+        SSR_HF              the same from the sums over k > L/4)
+    A value is NaN where its denominator is 0 (or negative from rounding), and the spread entries are NaN for S = 1."""
+    S = _num_samples(S)
+    counts = [int(c) for c in torch.as_tensor(counts).detach().cpu().reshape(-1).tolist()]
+    nb = len(counts)
+    if L is None:  # only a square image's scale can be read off its counts: they must be radial_bins(L, L)'s own
+        L = math.isqrt(sum(counts))
+        if L < 1 or L * L != sum(counts) or ops.radial_bins(L, L)[1].tolist() != counts:
+            raise ValueError("spectrum_summary: counts are not those of a square image; pass L = max(H, W)")
+    nan = float("nan")
+    keys = ("output", "target", "residual") + (("members", "member_residuals") if S > 1 else ())
+    pooled, n = {}, None
+    for key in keys:
+        t = torch.as_tensor(spectra[key], dtype=torch.float64).detach().cpu()
+        t = t.reshape(-1, S, nb) if key.startswith("member") else t.reshape(-1, nb)
+        if n is not None and t.shape[0] != n:
+            raise ValueError(f"spectrum_summary: {t.shape[0]} rows of {key}, {n} of output")
+        n = t.shape[0]
+        pooled[key] = t.sum(dim=0).tolist()
+
+    def div(a, b):
+        return a / b if b > 0 else nan
+
+    def root(a):
+        return math.sqrt(a) if a >= 0 else nan
+
+    psd = {key: [div(v, n * c) for v, c in zip(pooled[key], counts)] for key in ("output", "target", "residual")}
+    out = dict(n=n, PSD_output=psd["output"], PSD_target=psd["target"], PSD_residual=psd["residual"])
+    tot = {"output": pooled["output"], "target": pooled["target"], "residual": pooled["residual"]}
+    if S > 1:
+        tot["member"] = [sum(pooled["members"][s][k] for s in range(S)) / S for k in range(nb)]
+        tot["member_residual"] = [sum(pooled["member_residuals"][s][k] for s in range(S)) / S for k in range(nb)]
+        out["PSD_member"] = [div(v, n * c) for v, c in zip(tot["member"], counts)]
+        out["PSD_member_residual"] = [div(v, n * c) for v, c in zip(tot["member_residual"], counts)]
+    hf = [k for k in range(nb) if 4 * k > L]
+    for tag in ("output",) + (("member",) if S > 1 else ()):
+        ratio = [div(a, b) for a, b in zip(tot[tag], tot["target"])]
+        out["RATIO_" + tag] = ratio
+        out["HF_RATIO_" + tag] = div(sum(tot[tag][k] for k in hf), sum(tot["target"][k] for k in hf))
+        db = [10.0 * math.log10(tot[tag][k] / tot["target"][k]) for k in range(1, nb) if 2 * k <= L and tot[tag][k] > 0 and tot["target"][k] > 0]
+        out["LSD_" + tag] = math.sqrt(sum(d * d for d in db) / len(db)) if db else nan
+    if S > 1:
+        spread = [S / (S - 1) * (a - b) for a, b in zip(tot["member"], tot["output"])]  # power sums; the PSDs divide both by n counts
+        out["SPREAD_PSD"] = [div(v, n * c) for v, c in zip(spread, counts)]
+        out["SSR_k"] = [root(div((S + 1) / S * a, b)) for a, b in zip(spread, tot["residual"])]
+        out["SSR_HF"] = root(div((S + 1) / S * sum(spread[k] for k in hf), sum(tot["residual"][k] for k in hf)))
+    else:
+        out["SPREAD_PSD"], out["SSR_k"], out["SSR_HF"] = [nan] * nb, [nan] * nb, nan
+    out["SKILL_PSD"] = psd["residual"]
+    return out
+
+
 def ensemble_distance_summary(d2, counts, S, has_target):
     """The image-level scores of an S-member ensemble from what ops.ensemble_distances returns, on the host in float64:
         d2 [..., M, M] squared distances between an image's M = S + has_target rows (members, then the target); counts [..., 2] =
@@ -1354,6 +1424,43 @@ class driftSDE:
             raise ValueError(f"member_distances: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
                              f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
         return ops.ensemble_distances(samples.contiguous(), None if target is None else target.contiguous())
+
+    @staticmethod
+    def power_spectra(samples_or_output, target=None):
+        """Radial power spectra of an ensemble's samples [B, S, C, H, W] (reverse_ddpm_ensemble(..., return_samples=True)) or of one
+        restoration [B, C, H, W] (S = 1), with target [B, C, H, W] when given -> a dict of float64 per-bin power sums on the device
+        (ops.radial_power_spectrum; bins, their point counts and frequencies: ops.radial_bins(H, W)):
+            output [B, C, nb]                 the restoration; for samples their per-pixel mean (ops.ensemble_stats)
+            members [B, C, S, nb]             every member (samples only)
+            target, residual [B, C, nb]       the truth, and output - target          (with a target)
+            member_residuals [B, C, S, nb]    member - target                         (samples and a target)
+        The differences are formed in fp64 inside the kernel.  One radial_power_spectrum call for the planes themselves and one for
+        the residual planes, no host copy; spectrum_summary(spectra, counts, S) reads the ratios and the spread-skill curve off it."""
+        x = samples_or_output
+        if not torch.is_tensor(x) or x.dim() not in (4, 5):
+            raise ValueError("power_spectra: takes samples [B, S, C, H, W] or an output [B, C, H, W]")
+        if x.dim() == 5:
+            B, S, Cn = x.shape[:3]
+            mean, _ = ops.ensemble_stats(x.contiguous())
+            rows = torch.cat([mean.unsqueeze(1), x], dim=1).transpose(1, 2)  # [B, C, 1 + S, H, W]: the mean, then the members
+        else:
+            (B, Cn), S = x.shape[:2], 0
+            rows = x.unsqueeze(2)
+        if target is not None and (not torch.is_tensor(target) or tuple(target.shape) != (B, Cn) + tuple(x.shape[-2:])):
+            raise ValueError(f"power_spectra: target must be [B, C, H, W] = {(B, Cn) + tuple(x.shape[-2:])}, got "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+        planes = rows if target is None else torch.cat([rows, target.unsqueeze(2)], dim=2)
+        own = ops.radial_power_spectrum(planes.contiguous())  # [B, C, 1 + S (+ 1), nb]
+        out = dict(output=own[:, :, 0])
+        if S:
+            out["members"] = own[:, :, 1:1 + S]
+        if target is not None:
+            out["target"] = own[:, :, 1 + S]
+            res = ops.radial_power_spectrum(rows.contiguous(), sub=target.contiguous(), sub_rep=1 + S)
+            out["residual"] = res[:, :, 0]
+            if S:
+                out["member_residuals"] = res[:, :, 1:]
+        return out
 
     @staticmethod
     def _order_stats(samples, level):

@@ -314,6 +314,16 @@ class CLIPDriftModel():
         from .. import ops
         return ops.ensemble_pick_rows(self.samples.contiguous(), held[2], 0 if which == "medoid" else 1)
 
+    def power_spectra(self, with_target=True):
+        """radial power spectra of what test() left (driftSDE.power_spectra): of the members in self.samples and their mean after
+        test(return_samples=True), else of self.output (the plain chain: S = 1), against self.target when with_target -> a dict of
+        float64 [B, C, (S,) nb] power sums on the device; spectrum_summary(spectra, ops.radial_bins(H, W)[1], S) turns them into
+        PSDs, the ratios to the truth's spectrum and the per-frequency spread-skill curve."""
+        if getattr(self, "output", None) is None:
+            raise ValueError("power_spectra: no output is held; run test() first")
+        held = self.samples if getattr(self, "samples", None) is not None else self.output
+        return self.sde.power_spectra(held, self.target if with_target else None)
+
     def get_visuals(self):
         return self.visuals
 

@@ -2,6 +2,7 @@
 stream; every arithmetic operation below runs in the hand-written HIP kernels.  No fallbacks."""
 import contextlib
 import ctypes as C
+import functools
 import math
 import os
 import threading
@@ -996,6 +997,91 @@ def ensemble_pick_rows(x, pick, col):
     check(lib.idiff_ensemble_pick_rows(_p(x), C.c_void_p(pick.data_ptr() + 4 * col), pick.shape[1], _p(out), B, S, n_s, _stream()),
           "ensemble_pick_rows")
     return out
+
+
+@functools.lru_cache(maxsize=16)
+def radial_bins(H, W):
+    """The radial frequency bins of an H x W image's half plane, on the host in exact integer arithmetic -> (bins int32 [H, Wh], counts
+    int64 [nb], freq float64 [nb]), Wh = W // 2 + 1.  With L = max(H, W), u' = min(u, H - u) and v' = v, the bin of (u, v) is the
+    largest integer k with (2k - 1)^2 H^2 W^2 <= 4 L^2 (u'^2 W^2 + v'^2 H^2): the nearest integer to L sqrt((u'/H)^2 + (v'/W)^2), ties
+    going up.  nb = the largest bin + 1; counts[k] = the bin's points of the full H x W plane (a half-plane point counts once for v = 0
+    and for v = W/2 with W even, else twice), so counts.sum() == H W; freq[k] = k / L cycles per pixel.  Cached: treat the tensors as
+    read-only."""
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
+        raise ValueError(f"radial_bins: H and W must be ints >= 1, got {H!r}, {W!r}")
+    Wh, L, D = W // 2 + 1, max(H, W), H * W
+    rows = []
+    for up in range(H // 2 + 1):
+        rows.append([(math.isqrt(4 * L * L * (up * up * W * W + v * v * H * H)) // D + 1) // 2 for v in range(Wh)])
+    table = [rows[min(u, H - u)] for u in range(H)]
+    nb = max(max(row) for row in table) + 1
+    counts = [0] * nb
+    for row in table:
+        for v, k in enumerate(row):
+            counts[k] += 1 if v == 0 or 2 * v == W else 2
+    return (torch.tensor(table, dtype=torch.int32), torch.tensor(counts, dtype=torch.int64),
+            torch.tensor([k / L for k in range(nb)], dtype=torch.float64))
+
+
+_radial_bins_dev = {}
+SPECTRUM_MAX_WS_BYTES = 256 << 20
+
+
+def radial_power_spectrum(x, sub=None, sub_rep=1, bins=None, nb=None, max_ws_bytes=SPECTRUM_MAX_WS_BYTES):
+    """x [..., H, W] -> float64 [..., nb]: per plane the power |DFT|^2 / (H W) summed over the radial bins of radial_bins(H, W), the
+    full frequency plane counted (so the bins of a plane add up to the sum of its squares).  With sub [..., H, W] of R / sub_rep planes
+    the plane r is (double)x[r] - (double)sub[r // sub_rep]: residual spectra without a temporary.  fp64 on the matrix cores, no
+    atomics, no host copy; a plane with a NaN or inf gives NaN in all its bins (idiff_radial_power_spectrum, include/idiff.h).  The
+    bin table is uploaded once per (H, W, device); bins (int32 [H, Wh] on the device) and nb replace it: an entry outside [0, nb) drops
+    its point.  The planes go in chunks whose workspace stays within max_ws_bytes; a plane's bits do not depend on the chunking."""
+    lib = _lib.load()
+    _c(x, "x"), _c(sub, "sub")
+    assert x.dim() >= 2, "radial_power_spectrum: x is [..., H, W]"
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    R = 1
+    for d in x.shape[:-2]:
+        R *= int(d)
+    if bins is None:
+        key = (H, W, x.device)
+        if key not in _radial_bins_dev:
+            if not (1 <= H <= 1024 and 1 <= W <= 1024):
+                raise _lib.IdiffError(f"radial_power_spectrum: H = {H}, W = {W} are outside [1, 1024]")
+            table, counts, _ = radial_bins(H, W)
+            _radial_bins_dev[key] = (table.to(x.device), int(counts.numel()))
+        bins, nb = _radial_bins_dev[key]
+    else:
+        _c(bins, "bins", torch.int32)
+        assert tuple(bins.shape) == (H, W // 2 + 1), "radial_power_spectrum: bins is [H, W // 2 + 1]"
+        if isinstance(nb, bool) or not isinstance(nb, int):
+            raise _lib.IdiffError(f"radial_power_spectrum: nb must be an int beside bins, got {nb!r}")
+    if sub is not None:
+        if isinstance(sub_rep, bool) or not isinstance(sub_rep, int) or sub_rep < 1 or R % sub_rep:
+            raise _lib.IdiffError(f"radial_power_spectrum: sub_rep = {sub_rep!r} does not divide the {R} planes of x")
+        if tuple(sub.shape[-2:]) != (H, W) or sub.numel() != (R // sub_rep) * H * W:
+            raise _lib.IdiffError(f"radial_power_spectrum: sub holds {tuple(sub.shape)}, not {R // sub_rep} planes of {H} x {W}")
+    out = torch.empty(tuple(x.shape[:-2]) + (max(nb, 0),), device=x.device, dtype=torch.float64)
+    # rows per call: the workspace rule is the library's; groups of sub_rep rows stay together while one group fits
+    rows = min(max(R, 1), 65535)
+    while rows > 1 and int(lib.idiff_radial_power_spectrum_ws_bytes(rows, H, W)) > max_ws_bytes:
+        rows = max(1, min(rows - 1, rows * max_ws_bytes // int(lib.idiff_radial_power_spectrum_ws_bytes(rows, H, W))))
+    group = sub_rep if sub is not None else 1
+    if rows >= group:
+        rows -= rows % group
+    ws = torch.empty((max(int(lib.idiff_radial_power_spectrum_ws_bytes(rows, H, W)), 8) // 8,), device=x.device, dtype=torch.float64)
+    r0 = 0
+    while True:
+        n = min(rows, R - r0)
+        rep = group
+        if sub is not None and rows < group:  # a chunk inside one group of rows: they all take the same plane of sub
+            n = min(n, group - r0 % group)
+            rep = n
+        check(lib.idiff_radial_power_spectrum(C.c_void_p(x.data_ptr() + 4 * r0 * H * W),
+                                              None if sub is None else C.c_void_p(sub.data_ptr() + 4 * (r0 // group) * H * W), rep,
+                                              C.c_void_p(bins.data_ptr()), nb, C.c_void_p(out.data_ptr() + 8 * r0 * max(nb, 0)),
+                                              C.c_void_p(ws.data_ptr()), n, H, W, _stream()), "radial_power_spectrum")
+        r0 += n
+        if r0 >= R:
+            return out
 
 
 def dihedral_rows(x, codes, S=None, in_rep=1, out=None):

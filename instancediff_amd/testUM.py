@@ -15,6 +15,10 @@ pooled scores are printed and the pooled rank histogram goes to `rank_hist.json`
 With `--distances` on top of `--num-samples S` the members are compared as whole images on the device: the energy score `ES`, its fair form
 `ES_FAIR` and the mean pairwise member distance `DIVERSITY` are listed per image with `PSNR_best` (the member nearest to the ground truth) and
 `PSNR_medoid` (the most central member), and the medoid is written as `<i>_medoid_WxHx1.raw`.
+With `--spectra` (with or without `--num-samples`) the restoration is compared with the ground truth scale by scale on the device: per image
+`HF_RATIO` (the restored power above half Nyquist over the truth's: below 1 is over-smoothing) and `LSD` (the log-spectral distance in dB), with
+`--num-samples S` also `HF_RATIO_member`, `LSD_member` and `SSR_HF` (the spread-skill ratio of the frequencies above half Nyquist); the radial
+power spectra go to `<i>_spectra.json`, the pooled ones per artifact type to `spectra.json` (`spectra_WxH.json` per size if a type's images differ in size).
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
@@ -35,7 +39,18 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary
+from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary, spectrum_summary
+
+
+def pool_spectra(entries, S):
+    """entries: (H, W, spectra dict of host tensors) per image -> {(H, W): spectrum_summary of the images of that size pooled}.  Bins of
+    different image sizes are different frequencies, so a type whose images differ in size gets a record per size."""
+    out = {}
+    for Hs, Ws in sorted({(h, w) for h, w, _ in entries}):
+        group = [sp for h, w, sp in entries if (h, w) == (Hs, Ws)]
+        out[(Hs, Ws)] = spectrum_summary({key: torch.cat([sp[key] for sp in group]) for key in group[0]}, ops.radial_bins(Hs, Ws)[1], S,
+                                         L=max(Hs, Ws))
+    return out
 
 
 def main(argv=None):
@@ -61,6 +76,9 @@ def main(argv=None):
     parser.add_argument("--distances", action="store_true",
                         help="image-level member distances (needs num_samples > 1): the energy score ES / ES_FAIR, DIVERSITY, PSNR_best and "
                              "PSNR_medoid per image and the medoid member as a map, the averages per artifact type")
+    parser.add_argument("--spectra", action="store_true",
+                        help="radial power spectra of the restoration, the ground truth and their difference (of the members too with "
+                             "num_samples > 1): HF_RATIO and LSD per image, <i>_spectra.json, the pooled spectra in spectra.json per artifact type")
     parser.add_argument("--tile", type=int, nargs="+", default=None, metavar="P",
                         help="driftSDE tile: window size P, or Ph Pw, of tiled sampling for images larger than the window (overrides the YAML)")
     parser.add_argument("--tile-overlap", type=int, default=None, metavar="O",
@@ -143,6 +161,11 @@ def main(argv=None):
     if args.distances:
         for r in results.values():
             r['ES'], r['ES_FAIR'], r['DIVERSITY'], r['PSNR_best'], r['PSNR_medoid'] = [], [], [], [], []
+    if args.spectra:
+        for r in results.values():
+            r['HF_RATIO'], r['LSD'], r['spectra'] = [], [], []
+            if S > 1:
+                r['HF_RATIO_member'], r['LSD_member'], r['SSR_HF'] = [], [], []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -211,6 +234,21 @@ def main(argv=None):
                     m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_medoid_{m.shape[-1]}x{m.shape[-2]}x1.raw"))
                     extra += (f", ES={r['ES'][-1]}, ES_FAIR={r['ES_FAIR'][-1]}, DIVERSITY={r['DIVERSITY'][-1]}, PSNR_best={r['PSNR_best'][-1]}, "
                               f"PSNR_medoid={r['PSNR_medoid'][-1]}")
+                if args.spectra:  # the power of the [-1, 1] tensors times 0.25: RMSE's x/2 + 0.5 scale but for bin 0, which no ratio uses
+                    spectra = {key: 0.25 * v.cpu() for key, v in model.power_spectra().items()}
+                    Hs, Ws = model.output.shape[-2:]
+                    _, bin_counts, freq = ops.radial_bins(int(Hs), int(Ws))
+                    one = spectrum_summary(spectra, bin_counts, S, L=max(int(Hs), int(Ws)))
+                    r['spectra'].append((int(Hs), int(Ws), spectra))
+                    r['HF_RATIO'].append(one['HF_RATIO_output']), r['LSD'].append(one['LSD_output'])
+                    extra += f", HF_RATIO={r['HF_RATIO'][-1]}, LSD={r['LSD'][-1]}"
+                    if S > 1:
+                        r['HF_RATIO_member'].append(one['HF_RATIO_member']), r['LSD_member'].append(one['LSD_member'])
+                        r['SSR_HF'].append(one['SSR_HF'])
+                        extra += f", HF_RATIO_member={r['HF_RATIO_member'][-1]}, LSD_member={r['LSD_member'][-1]}, SSR_HF={r['SSR_HF'][-1]}"
+                    with open(os.path.join(result_root, it["name"], f"{i}_spectra.json"), "w") as f:
+                        json.dump(dict(S=S, freq=freq.tolist(), counts=bin_counts.tolist(),
+                                       **{key: v for key, v in one.items() if key.startswith("PSD_")}), f)
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -228,6 +266,20 @@ def main(argv=None):
                       f"invalid: {pooled['invalid']}")
                 with open(os.path.join(result_root, k, "rank_hist.json"), "w") as f:
                     json.dump(dict(S=S, hist=pooled['hist'], N=pooled['N'], nominal=1.0 / (S + 1), invalid=pooled['invalid']), f)
+    if args.spectra:  # the type's record: the power sums pooled over its images, not the mean of the per-image ratios; per image size
+        for k, v in results.items():
+            v['pooled_spectra'] = pool_spectra(v.get('spectra', []), S)
+            sizes = sorted(v['pooled_spectra'])
+            for Hs, Ws in sizes:
+                pooled = v['pooled_spectra'][(Hs, Ws)]
+                group = [sp for h, w, sp in v['spectra'] if (h, w) == (Hs, Ws)]
+                _, bin_counts, freq = ops.radial_bins(Hs, Ws)
+                of_size = "" if len(sizes) == 1 else f" of {Ws}x{Hs}"
+                print(f"{k}, spectra pooled over {len(group)} images{of_size}: HF_RATIO: {pooled['HF_RATIO_output']}, LSD: {pooled['LSD_output']}"
+                      + (f", HF_RATIO_member: {pooled['HF_RATIO_member']}, LSD_member: {pooled['LSD_member']}, SSR_HF: {pooled['SSR_HF']}"
+                         if S > 1 else ""))
+                with open(os.path.join(result_root, k, "spectra.json" if len(sizes) == 1 else f"spectra_{Ws}x{Hs}.json"), "w") as f:
+                    json.dump(dict(S=S, H=Hs, W=Ws, images=len(group), freq=freq.tolist(), counts=bin_counts.tolist(), **pooled), f)
     if times:
         print(f"mean sampling time per image: {sum(times) / len(times):.3f} s ({getattr(sde, 'last_steps', sde.T)} steps)"
               + (f", solver order {sde.last_solver_order}" if hasattr(sde, 'last_solver_order') else "")
