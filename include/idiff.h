@@ -825,7 +825,15 @@ int idiff_mse_loss(const float* a, const float* b, float* loss, float* grad, flo
                    idiff_stream_t stream);
 /* validation metrics of the drivers (trainUM.py:314-329, testUM.py:151-164) on x/2+0.5, data_range 1:
  * out_b3[b] = {RMSE, PSNR dB, SSIM (skimage: gaussian 11x11 sigma 1.5, K1 .01, K2 .03, interior crop)};
- * pred/target [B,H,W]; ws: B*128 floats */
+ * pred/target [B,H,W]; ws: B*128 floats.
+ * SSIM is NaN, not 0, for H < 11 or W < 11 (no pixel has a whole window; skimage refuses such an image); RMSE and PSNR are as ever.
+ * Operation order, fp32: per interior pixel the five window moments are accumulated on values shifted by the window-centre pixels,
+ * da = 0.5 (p - p0), dc = 0.5 (t - t0) (sum w da, sum w dc, sum w da^2, sum w dc^2, sum w da dc; the variances and the covariance are
+ * shift-invariant, the means get (0.5 p0 + 0.5), (0.5 t0 + 0.5) added back), so a locally flat bright or saturated region does not
+ * cancel against C2 = 9e-4 as raw moments sum w a^2 - (sum w a)^2 do; the final quotient runs without FMA contraction, so pred ==
+ * target gives exactly 1.  Pixel values are summed by thread i of 64 x 256 over pixels i, i + 16384, ..., a 64-lane butterfly, the four
+ * waves of a workgroup in order, and the 64 partials of an image in fp64.  A null pointer or B, H or W < 1: IDIFF_E_BADARG, nothing
+ * launched. */
 int idiff_image_metrics(const float* pred, const float* target, float* out_b3, float* ws, int B, int H, int W,
                         idiff_stream_t stream);
 /* torch.optim.Adam semantics (L2-in-gradient weight decay, config.yml:138-143), grad pre-scaled by grad_scale

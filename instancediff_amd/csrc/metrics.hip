@@ -2,6 +2,17 @@
 // and SSIM with skimage's settings (gaussian_weights=True, sigma=1.5 -> 11x11 window, use_sample_covariance=False,
 // K1=.01, K2=.03, data_range=1, mean over the interior cropped by (win-1)/2) on images mapped x/2+0.5.
 // Replaces a per-image device->host copy + skimage call by one launch per batch and one [B,3] read-back.
+//
+// Operation order (fp32 unless said; tests/image_metrics_ref.py restates it).  Per interior pixel the five window moments are taken on
+// values shifted by the window-centre pixels, da = 0.5 (p - p0), dc = 0.5 (t - t0):  sx = sum w da, sy = sum w dc, sxx = sum w da^2,
+// syy = sum w dc^2, sxy = sum w da dc over the 11x11 window, row by row;  vx = sxx - sx^2, vy = syy - sy^2, vxy = sxy - sx sy (variances
+// and the covariance do not see a shift) and the means get the shifts back, ux = (0.5 p0 + 0.5) + sx, uy = (0.5 t0 + 0.5) + sy.  Raw
+// moments sum w a^2 - (sum w a)^2 lose a^2 2^-24 sqrt(121) to rounding, against C2 = 9e-4 in the denominator: up to 6e-4 of SSIM on a
+// locally flat bright image, which is what clamped CT and cryo-EM data are made of.  The quotient is evaluated without FMA contraction,
+// so that its numerator and denominator are the same roundings of the same numbers when pred == target (SSIM exactly 1).
+// Reduction: thread i of 64 x 256 adds the values of pixels i, i + 16384, ...; a 64-lane xor butterfly; the workgroup's four waves as
+// (w0 + w1) + (w2 + w3); metrics_final_kernel sums the 64 partials of an image in fp64, in order.
+// H < 11 or W < 11: no pixel has a whole window and SSIM is NaN (skimage refuses such an image), not 0.
 #include <math.h>
 
 #include "common.h"
@@ -10,6 +21,12 @@ namespace {
 
 constexpr int SS_R = 5;  // radius: int(3.5 * 1.5 + 0.5)
 constexpr int SS_PARTS = 64;
+
+__device__ __forceinline__ float ssim_index(float ux, float uy, float vx, float vy, float vxy) {
+#pragma clang fp contract(off)
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    return ((2.f * ux * uy + C1) * (2.f * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+}
 
 __global__ __launch_bounds__(256) void metrics_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt, float* __restrict__ part,
                                                               int H, int W) {
@@ -27,7 +44,6 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(const float* __res
     __syncthreads();
     const float* p = pred + (long long)b * H * W;
     const float* t = tgt + (long long)b * H * W;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     float sse = 0.f, ssim = 0.f;
     const int n = H * W;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -35,22 +51,23 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(const float* __res
         const float d = 0.5f * (p[i] - t[i]);  // (p/2+0.5) - (t/2+0.5)
         sse += d * d;
         if (y >= SS_R && y < H - SS_R && x >= SS_R && x < W - SS_R) {
-            float ux = 0.f, uy = 0.f, uxx = 0.f, uyy = 0.f, uxy = 0.f;
+            const float p0 = p[i], t0 = t[i];
+            float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
             for (int dy = -SS_R; dy <= SS_R; ++dy) {
                 const float wy = w1[dy + SS_R];
                 for (int dx = -SS_R; dx <= SS_R; ++dx) {
                     const float w = wy * w1[dx + SS_R];
-                    const float a = 0.5f * p[(y + dy) * W + x + dx] + 0.5f;
-                    const float c = 0.5f * t[(y + dy) * W + x + dx] + 0.5f;
-                    ux += w * a;
-                    uy += w * c;
-                    uxx += w * a * a;
-                    uyy += w * c * c;
-                    uxy += w * a * c;
+                    const float a = 0.5f * (p[(y + dy) * W + x + dx] - p0);
+                    const float c = 0.5f * (t[(y + dy) * W + x + dx] - t0);
+                    sx += w * a;
+                    sy += w * c;
+                    sxx += w * a * a;
+                    syy += w * c * c;
+                    sxy += w * a * c;
                 }
             }
-            const float vx = uxx - ux * ux, vy = uyy - uy * uy, vxy = uxy - ux * uy;
-            ssim += ((2.f * ux * uy + C1) * (2.f * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+            const float vx = sxx - sx * sx, vy = syy - sy * sy, vxy = sxy - sx * sy;
+            ssim += ssim_index((0.5f * p0 + 0.5f) + sx, (0.5f * t0 + 0.5f) + sy, vx, vy, vxy);
         }
     }
     sse = wave_sum(sse);
@@ -78,7 +95,7 @@ __global__ void metrics_final_kernel(const float* __restrict__ part, float* __re
     const double inner = (double)(H - 2 * SS_R) * (double)(W - 2 * SS_R);
     out[b * 3 + 0] = (float)sqrt(mse);
     out[b * 3 + 1] = (float)(10.0 * log10(1.0 / mse));
-    out[b * 3 + 2] = inner > 0 ? (float)(ss / inner) : 0.f;
+    out[b * 3 + 2] = (H > 2 * SS_R && W > 2 * SS_R) ? (float)(ss / inner) : nanf("");
 }
 
 }  // namespace

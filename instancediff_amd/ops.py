@@ -709,7 +709,12 @@ def scoremap(feat, tv, idx=None):
 
 
 def image_metrics(pred, target):
-    """pred/target [B,H,W] in [-1,1] -> [B,3] = (RMSE, PSNR dB, SSIM) on x/2+0.5, data_range 1 (device tensor)."""
+    """pred/target [B,H,W] in [-1,1] -> [B,3] = (RMSE, PSNR dB, SSIM) on x/2+0.5, data_range 1 (device tensor).
+
+    SSIM is NaN for H < 11 or W < 11 (no pixel has a whole 11x11 window; skimage refuses such an image), not 0.  The window moments are
+    accumulated in fp32 on values shifted by the window-centre pixels (variances and the covariance are shift-invariant; the means get
+    the shifts back), which keeps locally flat bright or saturated regions from cancelling against C2 = 9e-4; pixel values are summed by
+    64 x 256 threads striding the image, a wave butterfly, four waves in order and 64 partials in fp64 (include/idiff.h)."""
     lib = _lib.load()
     pred, target = pred.contiguous(), target.contiguous()
     _c(pred, "pred"), _c(target, "target")
