@@ -628,6 +628,46 @@ int idiff_ensemble_pick_rows(const float* x, const int32_t* pick, int pick_strid
 int idiff_radial_power_spectrum(const float* x, const float* sub, int sub_rep, const int32_t* bins, int nb, double* out, void* ws, int R,
                                 int H, int W, idiff_stream_t stream);
 int64_t idiff_radial_power_spectrum_ws_bytes(int R, int H, int W);
+/* Sparsification curves of an uncertainty map: key, pred, target [B][n_s] -> per image and per point k = 0 .. K-1 of the
+ * curve the error above and at the key's threshold of rank floor(k N / K), from which the host reads the error that remains after the
+ * k/K most uncertain pixels are removed (models/SDEs/driftSDE.py: sparsification_summary).  Per pixel, each rounded once in fp32, no
+ * contraction:
+ *   d = pred - target ;  e = d*d
+ * With key == NULL the ranking key is e itself (the oracle curve).  A pixel is invalid iff its key or its e is NaN: it is counted in
+ * `invalid` and adds nowhere else.  +-inf keys are values and rank at the ends; an infinite e is a value and makes the sums it enters
+ * non-finite.
+ * Order: the key's 32 bits b become a uint32 u: 0x80000000 (-0) is first replaced by 0, in integers (no float add: denormals are
+ * never touched), then u = (b >> 31) ? ~b : b | 0x80000000.  So -0 and +0 tie, denormals are distinct, and every non-NaN float has a
+ * place.  With N the valid pixels of the image, for k = 0 .. K-1:
+ *   m_k   = floor(k N / K), in 64-bit integers
+ *   tau_k = the m_k-th largest u, counted 1-based with multiplicity
+ * and for m_k = 0 (always k = 0; larger k too when N < K) the entry is the sentinel: tau = NaN (0x7fc00000), zero counts, +0.0 sums.
+ *   counts int32 [B][K+1][2]    row k = {c_k = #{u > tau_k}, t_k = #{u == tau_k}};  row K = {N, invalid}
+ *   sums   float64 [B][K+1][2]  row k = {A_k = sum of e over u > tau_k, T_k = sum of e over u == tau_k};  row K = {sum of e over the
+ *                               valid pixels, +0.0}
+ *   tau    fp32 [B][K]          the key at the threshold: the bits of the input pixel's key after the -0 -> +0 step
+ *   ws     idiff_sparsification_ws_bytes(B, K, n_s) bytes, 8-byte aligned; 0 for sizes the call refuses
+ * The error removed at point k is R_k = A_k + (m_k - c_k) T_k / t_k on the host: the expectation over a uniformly random order inside
+ * the tie group, so the curve does not depend on how any sort would break ties (c_k < m_k <= c_k + t_k always).
+ * Counts and tau are exact.  Sums are fp64 adds of the widened fp32 e in a fixed order.
+ * Three launches, no sort.  (1) The selection, one block of 1024 threads per image: a most-significant-digit-first radix selection of
+ * all K - 1 thresholds at once, four passes of 8 bits.  Pass 0 reads key / pred / target once, writes u (0 for an invalid pixel: no
+ * valid u is 0) to ws and counts u's top byte, which also gives N; passes 1 .. 3 read u back (from L2 at the project's sizes).  Per
+ * pass there is one 256-bin int32 histogram in LDS per distinct live prefix (at most 63, 63.2 KiB); the thresholds are monotone in k,
+ * so a pixel finds its prefix by a binary search over the sorted prefixes, and equal prefixes share a histogram; the bins take
+ * integer LDS adds (exact, the only atomics).  (2) The sums, 64 x B x ceil(K / 8) blocks of 256 threads, one float4 per lane,
+ * grid-stride: a block owns eight thresholds of an image, a thread keeps their A, T, c, t in registers (one compare and one predicated
+ * add each) and adds its pixels in loop order, a float4's elements in index order; then idiff_ensemble_scores' reduction, a fixed
+ * xor-shuffle tree per wave, the four waves in index order, one partial per block and quantity.  (3) One block per image adds the 64
+ * partials of every quantity in index order and writes the rows.  No float atomics, no global atomics: the result of image b depends
+ * on its own pixels, n_s and K only, not on B, its position in the batch or the run.  A threshold read back from ws is compared,
+ * never used as an address.
+ * 1 <= K <= 64, 1 <= B <= 65535, n_s % 4 == 0, n_s < 2^31; key / pred / target 16-byte aligned, sums / ws 8-byte aligned; sums, counts,
+ * tau and ws overlap neither each other nor the inputs.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as
+ * it was. */
+int idiff_sparsification(const float* key, const float* pred, const float* target, int K, double* sums, int32_t* counts, float* tau, void* ws,
+                         int B, int64_t n_s, idiff_stream_t stream);
+int64_t idiff_sparsification_ws_bytes(int B, int K, int64_t n_s);
 /* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
  * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
  * the flips applied after the transposition:

@@ -200,6 +200,77 @@ def ensemble_score_summary(sums, counts, S):
                 hist=hist, invalid=invalid)
 
 
+def _sparsification_K(K):
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPARSIFICATION_MAX_K:
+        raise ValueError(f"sparsification: K must be an int in [1, {ops.SPARSIFICATION_MAX_K}], got {K!r}")
+    return K
+
+
+def _pooled_removal(sums, counts, K, who):
+    """rows of ops.sparsification's (sums, counts) -> the pooled (R[k], m[k], total, N, invalid): per row m_k = floor(k N / K) and
+    R_k = A_k + (m_k - c_k) T_k / t_k, the expected error of the m_k pixels removed under a random order inside the tie group"""
+    sums = torch.as_tensor(sums, dtype=torch.float64).detach().cpu().reshape(-1, K + 1, 2).tolist()
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, K + 1, 2).tolist()
+    if len(sums) != len(counts):
+        raise ValueError(f"sparsification_summary: {len(sums)} rows of {who} sums, {len(counts)} rows of counts")
+    R, m, total, N, invalid = [0.0] * K, [0] * K, 0.0, 0, 0
+    for s, c in zip(sums, counts):
+        n = c[K][0]
+        invalid += c[K][1]
+        if n == 0:
+            continue
+        N += n
+        total += s[K][0]
+        for k in range(K):
+            mk = k * n // K
+            if mk == 0:
+                continue
+            ck, tk = c[k]
+            m[k] += mk
+            R[k] += s[k][0] + ((mk - ck) * s[k][1] / tk if tk else 0.0)
+    return R, m, total, N, invalid
+
+
+def sparsification_summary(sums, counts, sums_oracle, counts_oracle, K):
+    """The sparsification curves of an uncertainty map from what ops.sparsification returns for the map (sums, counts) and for the
+    oracle (key=None: sums_oracle, counts_oracle), on the host in float64.  Rows (images) are pooled first: R_k, m_k, the totals and N
+    are summed over the rows before any division (a row with N = 0 adds nothing), which is the aggregate over several images; the
+    mean of per-image ratios is not.  ->  dict(
+        fractions   k/K, k = 0 .. K-1: the share of pixels removed
+        curve       (total - R_k)/(N - m_k): the mean squared error of the pixels that remain after the m_k most uncertain are removed
+        oracle      the same with the pixels removed by their error: the lowest curve any map can reach
+        random      total/N at every k: removal in random order
+        curve_norm, oracle_norm, random_norm    each divided by its k = 0 value
+        AUSE        the area between curve_norm and oracle_norm (trapezoid rule over fractions): 0 for a perfect ranking
+        AURG        the area between random_norm and curve_norm: <= 0 for a map no better than chance
+        AUSE_RMSE, AURG_RMSE    the same on the square roots of the curves
+        N, invalid  the map's pooled valid and invalid pixels)
+    K = 1 (one point, no area) or no valid pixel gives NaN areas.  Takes tensors, arrays or nested lists."""
+    K = _sparsification_K(K)
+    R, m, total, N, invalid = _pooled_removal(sums, counts, K, "the map's")
+    Ro, mo, total_o, No, _ = _pooled_removal(sums_oracle, counts_oracle, K, "the oracle's")
+    nan = float("nan")
+    frac = [k / K for k in range(K)]
+    curve = [(total - R[k]) / (N - m[k]) for k in range(K)] if N else [nan] * K
+    oracle = [(total_o - Ro[k]) / (No - mo[k]) for k in range(K)] if No else [nan] * K
+    random = [total / N if N else nan] * K
+
+    def norm(c):
+        return [v / c[0] if c[0] > 0 else nan for v in c]
+
+    def area(a, b):  # the trapezoid rule on a - b over the fractions
+        d = [x - y for x, y in zip(a, b)]
+        return sum(0.5 * (d[k] + d[k + 1]) * (frac[k + 1] - frac[k]) for k in range(K - 1)) if K > 1 else nan
+
+    def root(c):
+        return [math.sqrt(v) if v >= 0 else nan for v in c]
+
+    cn, on, rn = norm(curve), norm(oracle), norm(random)
+    cr, orr, rr = norm(root(curve)), norm(root(oracle)), norm(root(random))
+    return dict(fractions=frac, curve=curve, oracle=oracle, random=random, curve_norm=cn, oracle_norm=on, random_norm=rn,
+                AUSE=area(cn, on), AURG=area(rn, cn), AUSE_RMSE=area(cr, orr), AURG_RMSE=area(rr, cr), N=N, invalid=invalid)
+
+
 def spectrum_summary(spectra, counts, S, L=None):
     """The scale-by-scale scores of a restoration or an S-member ensemble from what driftSDE.power_spectra returns, on the host in
     float64.  spectra: a dict of per-bin power sums (ops.radial_power_spectrum) with the keys output, target, residual [..., nb] and
@@ -1411,6 +1482,22 @@ class driftSDE:
             raise ValueError(f"score_ensemble: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
                              f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
         return ops.ensemble_scores(samples.contiguous(), target.contiguous(), want_map=want_map)
+
+    @staticmethod
+    def sparsification(output, uncertainty, target, K=20):
+        """Sparsification records of an uncertainty map [B, ...] (output_std, an interval width, a CRPS map) for the restoration
+        output [B, ...] against target [B, ...] -> (sums, counts, sums_oracle, counts_oracle, tau) on the device: two
+        ops.sparsification calls, the map's and the oracle's (three launches each, no sort, no host copy);
+        sparsification_summary(sums, counts, sums_oracle, counts_oracle, K) reads the curves and AUSE / AURG off them."""
+        K = _sparsification_K(K)
+        for name, t in (("output", output), ("uncertainty", uncertainty), ("target", target)):
+            if not torch.is_tensor(t) or t.dim() < 2 or tuple(t.shape) != tuple(output.shape):
+                raise ValueError(f"sparsification: {name} must be a [B, ...] tensor of the output's shape, got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        output, target = output.contiguous(), target.contiguous()
+        sums, counts, tau = ops.sparsification(uncertainty.contiguous(), output, target, K)
+        sums_oracle, counts_oracle, _ = ops.sparsification(None, output, target, K)
+        return sums, counts, sums_oracle, counts_oracle, tau
 
     @staticmethod
     def member_distances(samples, target=None):

@@ -314,6 +314,26 @@ class CLIPDriftModel():
         from .. import ops
         return ops.ensemble_pick_rows(self.samples.contiguous(), held[2], 0 if which == "medoid" else 1)
 
+    def sparsification(self, K=20, key="std"):
+        """sparsification records of an uncertainty map of the ensemble test(return_samples=True) left, for self.output against
+        self.target (driftSDE.sparsification) -> (sums, counts, sums_oracle, counts_oracle, tau) on the device.  key: "std", the
+        members' spread output_std; "width", output_hi - output_lo (needs the sde's interval); "crps", the CRPS map of
+        score_ensemble(want_map=True): a key that knows the truth, for comparison."""
+        if key not in ("std", "width", "crps"):
+            raise ValueError(f'sparsification: key must be "std", "width" or "crps", got {key!r}')
+        if getattr(self, "samples", None) is None:
+            raise ValueError("sparsification: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        if key == "std":
+            unc = self.output_std
+        elif key == "width":
+            if self.output_lo is None or self.output_hi is None:
+                raise ValueError("sparsification: no interval maps are held; run test(return_samples=True) with the sde's interval set first")
+            from .. import ops
+            unc = ops.axpby(self.output_hi, self.output_lo, 1.0, -1.0)
+        else:
+            unc = self.score_ensemble(want_map=True)[2]
+        return self.sde.sparsification(self.output, unc, self.target, K=K)
+
     def power_spectra(self, with_target=True):
         """radial power spectra of what test() left (driftSDE.power_spectra): of the members in self.samples and their mean after
         test(return_samples=True), else of self.output (the plain chain: S = 1), against self.target when with_target -> a dict of

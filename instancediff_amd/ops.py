@@ -1004,6 +1004,33 @@ def ensemble_pick_rows(x, pick, col):
     return out
 
 
+SPARSIFICATION_MAX_K = 64
+
+
+def sparsification(key, pred, target, K=20):
+    """key (a per-pixel uncertainty, or None for the oracle: the squared error itself), pred, target [B, ...] -> (sums float64
+    [B, K + 1, 2], counts int32 [B, K + 1, 2], tau [B, K]), all on the device: per image and point k of the sparsification curve the
+    sum of (pred - target)^2 and the number of pixels whose key is above / equal to the key of rank floor(k N / K) (row k), then the
+    total and (N, invalid) (row K); tau is that key (NaN where the rank is 0).  Three launches, no sort, no host copy; include/idiff.h
+    states the order, the arithmetic and the tie rule.  models/SDEs/driftSDE.py's sparsification_summary turns the (pooled) records of a
+    map and of the oracle into the curves and AUSE / AURG."""
+    lib = _lib.load()
+    _c(key, "key"), _c(pred, "pred"), _c(target, "target")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= SPARSIFICATION_MAX_K:
+        raise _lib.IdiffError(f"sparsification: K must be an int in [1, {SPARSIFICATION_MAX_K}], got {K!r}")
+    assert pred.dim() >= 2 and pred.shape == target.shape, "sparsification: pred and target are [B, ...] of one shape"
+    assert key is None or key.shape == pred.shape, "sparsification: key has the shape of pred"
+    B = pred.shape[0]
+    n_s = pred.numel() // B if B else 0
+    sums = torch.empty((B, K + 1, 2), device=pred.device, dtype=torch.float64)
+    counts = torch.empty((B, K + 1, 2), device=pred.device, dtype=torch.int32)
+    tau = torch.empty((B, K), device=pred.device, dtype=torch.float32)
+    ws = torch.empty((max(int(lib.idiff_sparsification_ws_bytes(B, K, n_s)), 8) // 8,), device=pred.device, dtype=torch.float64)
+    check(lib.idiff_sparsification(_p(key), _p(pred), _p(target), K, C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                   C.c_void_p(tau.data_ptr()), C.c_void_p(ws.data_ptr()), B, n_s, _stream()), "sparsification")
+    return sums, counts, tau
+
+
 @functools.lru_cache(maxsize=16)
 def radial_bins(H, W):
     """The radial frequency bins of an H x W image's half plane, on the host in exact integer arithmetic -> (bins int32 [H, Wh], counts

@@ -19,6 +19,10 @@ With `--spectra` (with or without `--num-samples`) the restoration is compared w
 `HF_RATIO` (the restored power above half Nyquist over the truth's: below 1 is over-smoothing) and `LSD` (the log-spectral distance in dB), with
 `--num-samples S` also `HF_RATIO_member`, `LSD_member` and `SSR_HF` (the spread-skill ratio of the frequencies above half Nyquist); the radial
 power spectra go to `<i>_spectra.json`, the pooled ones per artifact type to `spectra.json` (`spectra_WxH.json` per size if a type's images differ in size).
+With `--sparsification [K]` on top of `--num-samples S` the std map is tested as a ranking of the pixels by their error, on the device and without a
+sort: per image `AUSE` (the area between the map's sparsification curve and the oracle's: 0 is a perfect ranking), `AURG` (the area gained over
+removal in random order: <= 0 is no better than chance) and `AUSE_RMSE` are listed for K points (default 20), per artifact type the pooled values
+are printed and the pooled curves (mean squared errors on RMSE's x/2 + 0.5 scale) go to `sparsification.json`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
@@ -39,7 +43,7 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary, spectrum_summary
+from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary, sparsification_summary, spectrum_summary
 
 
 def pool_spectra(entries, S):
@@ -53,7 +57,12 @@ def pool_spectra(entries, S):
     return out
 
 
-def main(argv=None):
+def yaml_num_samples(args, opt):
+    """num_samples as the sde will get it: --num-samples, else the YAML's; known before the model is built"""
+    return args.num_samples if args.num_samples is not None else opt['sdes'][opt['test']['which_sde']].get('num_samples')
+
+
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-opt", type=str, required=True, help="Path to options YAML file.")
     parser.add_argument("--random-init", action="store_true", help="skip model.load (no checkpoint; synthetic smoke run)")
@@ -95,15 +104,34 @@ def main(argv=None):
                         help="driftSDE self_ensemble: member s of an ensemble runs on the image flipped (flips: any H x W) or flipped / "
                              "transposed (dihedral: square images) and is turned back before the reduction (needs num_samples > 1; "
                              "overrides the YAML)")
+    # absent from the namespace without the flag (argparse.SUPPRESS): tests/test_spectrum_cpu.py compares the whole namespace of a run
+    # without it against a literal dict
+    parser.add_argument("--sparsification", type=int, nargs="?", const=20, default=argparse.SUPPRESS, metavar="K",
+                        help="sparsification curves of the std map over K points, default 20 (needs num_samples > 1): AUSE / AURG / AUSE_RMSE "
+                             "per image, the pooled values and sparsification.json per artifact type; an image whose C*H*W is not a "
+                             "multiple of 4 is left out of the curves, with a note on its line")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
     if args.tile is not None and len(args.tile) > 2:
         parser.error("--tile takes one size P or two, Ph Pw")
     with open(args.opt, "r") as f:
         opt = yaml.load(f.read(), yaml.FullLoader)  # raw dict: missing keys raise, as in the reference (:50-54)
     if args.self_ensemble is not None:  # refused before the model is built: the option only turns the members of an ensemble
-        num = args.num_samples if args.num_samples is not None else opt['sdes'][opt['test']['which_sde']].get('num_samples')
+        num = yaml_num_samples(args, opt)
         if not isinstance(num, int) or num <= 1:
             parser.error("--self-ensemble turns the members of an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
+    K_sp = getattr(args, "sparsification", None)
+    if K_sp is not None:  # refused before the model is built, like --self-ensemble
+        if not 1 <= K_sp <= ops.SPARSIFICATION_MAX_K:
+            parser.error(f"--sparsification takes K in [1, {ops.SPARSIFICATION_MAX_K}]")
+        num = yaml_num_samples(args, opt)
+        if not isinstance(num, int) or num <= 1:
+            parser.error("--sparsification ranks the pixels by an ensemble's spread: it needs num_samples > 1 (--num-samples S or the YAML's "
+                         "num_samples)")
     rank, world, local = parallel.init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local if world > 1 else opt['gpu_ids'][0])
@@ -166,6 +194,9 @@ def main(argv=None):
             r['HF_RATIO'], r['LSD'], r['spectra'] = [], [], []
             if S > 1:
                 r['HF_RATIO_member'], r['LSD_member'], r['SSR_HF'] = [], [], []
+    if K_sp is not None:
+        for r in results.values():
+            r['AUSE'], r['AURG'], r['AUSE_RMSE'], r['sparsification'] = [], [], [], []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -249,6 +280,14 @@ def main(argv=None):
                     with open(os.path.join(result_root, it["name"], f"{i}_spectra.json"), "w") as f:
                         json.dump(dict(S=S, freq=freq.tolist(), counts=bin_counts.tolist(),
                                        **{key: v for key, v in one.items() if key.startswith("PSD_")}), f)
+                if K_sp is not None and model.output[0].numel() % 4:  # the kernel reads 16-byte pieces
+                    extra += ", AUSE=left out (C*H*W is not a multiple of 4)"
+                elif K_sp is not None:  # ratios of normalised curves: no scale to carry
+                    rec = [t.cpu() for t in model.sparsification(K=K_sp, key="std")[:4]]
+                    one = sparsification_summary(*rec, K_sp)
+                    r['sparsification'].append(rec)
+                    r['AUSE'].append(one['AUSE']), r['AURG'].append(one['AURG']), r['AUSE_RMSE'].append(one['AUSE_RMSE'])
+                    extra += f", AUSE={r['AUSE'][-1]}, AURG={r['AURG'][-1]}, AUSE_RMSE={r['AUSE_RMSE'][-1]}"
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -266,6 +305,18 @@ def main(argv=None):
                       f"invalid: {pooled['invalid']}")
                 with open(os.path.join(result_root, k, "rank_hist.json"), "w") as f:
                     json.dump(dict(S=S, hist=pooled['hist'], N=pooled['N'], nominal=1.0 / (S + 1), invalid=pooled['invalid']), f)
+    if K_sp is not None:  # the type's record: removed errors, ranks and totals pooled over its images, not the mean of the per-image areas
+        for k, v in results.items():
+            if not v['num'] or not v['sparsification']:
+                continue
+            pooled = sparsification_summary(*(torch.cat([rec[q] for rec in v['sparsification']]) for q in range(4)), K_sp)
+            v['pooled_sparsification'] = pooled
+            print(f"{k}, sparsification pooled over {len(v['sparsification'])} images: AUSE: {pooled['AUSE']}, AURG: {pooled['AURG']}, AUSE_RMSE: "
+                  f"{pooled['AUSE_RMSE']}, AURG_RMSE: {pooled['AURG_RMSE']}, invalid: {pooled['invalid']}")
+            with open(os.path.join(result_root, k, "sparsification.json"), "w") as f:  # curves of the [-1, 1] tensors times 0.25: RMSE's scale
+                json.dump(dict(S=S, K=K_sp, fractions=pooled['fractions'], curve=[0.25 * c for c in pooled['curve']],
+                               oracle=[0.25 * c for c in pooled['oracle']], random=[0.25 * c for c in pooled['random']], AUSE=pooled['AUSE'],
+                               AURG=pooled['AURG'], N=pooled['N'], invalid=pooled['invalid']), f)
     if args.spectra:  # the type's record: the power sums pooled over its images, not the mean of the per-image ratios; per image size
         for k, v in results.items():
             v['pooled_spectra'] = pool_spectra(v.get('spectra', []), S)
