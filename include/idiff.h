@@ -605,6 +605,58 @@ int64_t idiff_ensemble_distances_ws_bytes(int B, int S, int has_target);
  * table.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
 int idiff_ensemble_pick_rows(const float* x, const int32_t* pick, int pick_stride, float* out, int B, int S, int64_t n_s,
                              idiff_stream_t stream);
+/* Principal modes of an ensemble: d2 [B][M][M], what idiff_ensemble_distances wrote with M = S + has_target -> per image
+ * the eigen-decomposition of the members' centred Gram matrix, i.e. the PCA of the S members over the valid pixels, without another pass
+ * over the images.  Only the entries i < j of d2 are read; the diagonal counts as 0.  Centring about the centroid c of the S members, for
+ * all M rows, every sum in index order, every operation rounded once in fp64:
+ *   a_i  = (sum_{s<S} d2[i][s]) / S ;  abar = (sum_{s<S} a_s) / S ;  h_i = a_i - abar / 2                       = |r_i - c|^2
+ *   G_ij = ((h_i + h_j) - d2[i][j]) / 2                                                                          = <r_i - c, r_j - c>
+ * The member block G[:S][:S] is decomposed; with a target g_s = G[S][s] and tnorm2 = h_S, the squared error of the ensemble mean.
+ * Eigensolver: parallel cyclic two-sided Jacobi.  With Sp = S rounded up to even, a sweep is Sp - 1 rounds of Sp / 2 disjoint pairs by the
+ * round-robin schedule of idiff_ensemble_modes_pair.  A pair p < q is rotated iff |G_pq| > 2^-53 tr0, tr0 the trace before the first sweep,
+ * by Rutishauser's rotation: theta = (G_qq - G_pp) / (2 G_pq), t = sign(theta) / (|theta| + hypot(1, theta)) with sign(0) = +1,
+ * c = 1 / sqrt(t^2 + 1), s = t c; a column pair (x_p, x_q) becomes (c x_p - s x_q, s x_p + c x_q), rows likewise.  Per round, a block barrier
+ * between each: the rotations from the current matrix; all column updates of G and V; all row updates of G; the rotated pairs' entries
+ * set to exactly 0.  The solver stops after the first sweep that rotates nothing or after 32 sweeps: the run time is bounded whatever
+ * the matrix.
+ *   lam    float64 [B][S]     the eigenvalues in descending order, ties by original column index (a counting rank), as computed: not clamped
+ *   vec    float64 [B][S][S]  row k = the unit eigenvector of lam[k]; its component of largest magnitude is positive (the first on ties)
+ *   info   int32 [B][2]       {rank, sweeps}: mode k is live iff lam[0] > 0 and lam[k] > rel_floor lam[0], rank = the live modes (at most
+ *                             S - 1 in exact arithmetic); sweeps = the sweeps run, the last, idle one included, or -1 if 32 sweeps did not
+ *                             end the iteration (the outputs are written all the same)
+ *   coef   float64 [B][S][S]  row k = vec[k] / sqrt(lam[k]) for a live mode, zeros otherwise: u_k = sum_s coef[k][s] (x_s - c) is the mode
+ *                             image, of unit L2 norm over the valid pixels (idiff_ensemble_project)
+ *   tcoord float64 [B][S]     t_k = (sum_s vec[k][s] g_s) / sqrt(lam[k]) = <y - c, u_k>, fma in index order; +0.0 for a dead mode or
+ *                             without a target
+ *   tnorm2 float64 [B]        h_S; +0.0 without a target
+ * rel_floor must lie in (0, 1).  The Python surface passes 2^-30, which sits above the error bound of idiff_ensemble_distances' matrix,
+ * 2 (n + 2) 2^-53 relative for n valid pixels, only up to n of about 2^21: raise it for larger images.
+ * Degenerate images are no errors: S = 1, no valid pixel or all members equal (tr0 = 0) give rank 0, sweeps 0, lam all +0.0, vec the
+ * identity and coef zeros.  An image whose upper triangle holds a NaN, an infinite or a negative entry gets info = {-1, 0}, NaN in lam,
+ * tcoord and tnorm2 and zeros in vec and coef; other images are untouched.
+ * One launch, one block of 256 threads per image, fp64 throughout, G and V in LDS at a pitch of 65 doubles (66 560 bytes); no atomics,
+ * block barriers only.  The result of image b depends on its own matrix only: not on B, its place in the batch or the run.
+ * 1 <= S <= 64, 1 <= B <= 65535; every buffer 8-byte aligned, none overlapping another.  A refused call (IDIFF_E_BADARG) launches nothing
+ * and leaves every buffer as it was. */
+int idiff_ensemble_modes(const double* d2, int B, int S, int has_target, double rel_floor, double* lam, double* vec, double* coef,
+                         double* tcoord, double* tnorm2, int32_t* info, idiff_stream_t stream);
+/* The schedule idiff_ensemble_modes runs (the kernel and this entry point call one function), on the host, no GPU needed: pair i of round
+ * `round` for S members.  Sp = S rounded up to even, 0 <= round < Sp - 1, 0 <= i < Sp / 2: pair 0 is (round, Sp - 1), pair i >= 1 is
+ * ((round + i) mod (Sp - 1), (round - i) mod (Sp - 1)).  Returns 1 and *p < *q for a pair of members, 0 (and *p = *q = -1) for a pair that
+ * touches the padding index S of an odd S, which the solver skips, IDIFF_E_BADARG outside those ranges or for a null pointer. */
+int idiff_ensemble_modes_pair(int S, int round, int i, int* p, int* q);
+/* x [B][S][n_s], coefficients -> out [B][K][n_s] (fp32): out[b][k] = sum_s coef_b[k][s] (x[b][s] - c), c the per-pixel mean of the S
+ * members; coef_b = coef + b coef_image_stride holds K rows of S doubles (idiff_ensemble_modes' coef with stride S*S gives the K leading
+ * mode images; any coefficients are taken).  Per pixel in fp64, members in index order, every operation rounded once:
+ *   c = (((x_0 + x_1) + x_2) + ...) / S ;  acc_k = fma(coef[k][s], x_s - c, acc_k), acc_k = 0 at first ;  out = (float)acc_k
+ * A pixel where any member is NaN or infinite gets the quiet NaN 0x7fc00000 in all K planes.  One launch, grid = (at most 64 chunks, B),
+ * 256 threads, one float4 per lane and member, grid-stride; the K S coefficients go to LDS once per block (at most 4 KiB); a thread keeps
+ * its S float4 in registers for S <= 16 and reads them again above that; no atomics.
+ * 1 <= K <= 8, 1 <= S <= 64, 1 <= B <= 65535, n_s % 4 == 0, n_s < 2^31, coef_image_stride >= K S; x / out 16-byte aligned, coef 8-byte
+ * aligned; out overlaps neither x nor the coefficients.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it
+ * was. */
+int idiff_ensemble_project(const float* x, const double* coef, int64_t coef_image_stride, float* out, int B, int S, int K, int64_t n_s,
+                           idiff_stream_t stream);
 /* Radial power spectra of image rows: x [R][H][W], sub [R / sub_rep][H][W] or NULL, bins int32 [H][Wh], Wh = W/2 + 1
  * -> out float64 [R][nb].  Row r is the plane a = x[r], or a = (double)x[r] - (double)sub[r / sub_rep] (one exact fp64 subtraction per
  * pixel: residual spectra without a temporary).  With X[u,v] = sum_y sum_x a[y,x] exp(-2 pi i (u y / H + v x / W)) and

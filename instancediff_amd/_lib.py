@@ -139,6 +139,9 @@ SIGNATURES = {
     "idiff_ensemble_distances": (I, [P, P, P, P, P, P, I, I, I64, c_stream]),
     "idiff_ensemble_distances_ws_bytes": (I64, [I, I, I]),
     "idiff_ensemble_pick_rows": (I, [P, P, I, P, I, I, I64, c_stream]),
+    "idiff_ensemble_modes": (I, [P, I, I, I, C.c_double, P, P, P, P, P, P, c_stream]),
+    "idiff_ensemble_modes_pair": (I, [I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "idiff_ensemble_project": (I, [P, P, I64, P, I, I, I, I64, c_stream]),
     "idiff_radial_power_spectrum": (I, [P, P, I, P, I, P, P, I, I, I, c_stream]),
     "idiff_radial_power_spectrum_ws_bytes": (I64, [I, I, I]),
     "idiff_sparsification": (I, [P, P, P, I, P, P, P, P, I, I64, c_stream]),

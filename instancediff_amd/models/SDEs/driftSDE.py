@@ -403,6 +403,101 @@ def ensemble_distance_summary(d2, counts, S, has_target):
     return out
 
 
+def _mode_record(lams, ts, tnorm2, valid, S, has_target):
+    """the scores of one spectrum: lams / ts the live modes' eigenvalues and target coordinates (MODE_Z_RMS is the caller's)"""
+    nan = float("nan")
+    total = sum(lams)
+    one = dict(EXPLAINED=[nan] * S, EFF_MODES=nan, MODE_STD=[nan] * S, SPAN_SHARE=nan, MODE_Z=[nan] * S, MODE_Z_RMS=nan)
+    if lams and total > 0:
+        one["EFF_MODES"] = total * total / sum(v * v for v in lams)
+        for k, v in enumerate(lams):
+            one["EXPLAINED"][k] = v / total
+            if S > 1 and valid > 0 and v > 0:
+                one["MODE_STD"][k] = math.sqrt(v / ((S - 1) * valid))
+    if has_target:
+        if tnorm2 > 0:
+            one["SPAN_SHARE"] = sum(t * t for t in ts) / tnorm2
+        if S > 1:
+            for k, (v, t) in enumerate(zip(lams, ts)):
+                if v > 0:
+                    one["MODE_Z"][k] = t / math.sqrt(v / (S - 1) * (1 + 1 / S))
+    return one
+
+
+def ensemble_mode_summary(lam, tcoord, tnorm2, info, counts, S, has_target):
+    """What the principal modes of an S-member ensemble say, from what ops.ensemble_modes and ops.ensemble_distances return, on the host
+    in float64: lam [..., S], tcoord [..., S], tnorm2 [...], info [..., 2] = (rank, sweeps), counts [..., 2] = (valid, invalid) pixels.
+    The live modes of an image are its first `rank` ones.  Per image:
+        EXPLAINED[k]  lam_k / sum of the live lam: the share of the ensemble's variance along mode k
+        EFF_MODES     (sum lam)^2 / sum lam^2 over the live modes, the participation ratio: 1 for a single mode, S - 1 for an isotropic
+                      ensemble -- how many degrees of freedom the members really have
+        MODE_STD[k]   sqrt(lam_k / ((S - 1) valid)): the standard deviation along mode k as a per-pixel root mean square
+        SPAN_SHARE    sum of t_k^2 over the live modes / tnorm2: the share of the mean's squared error that lies inside the span of the
+                      members' variation (with a target)
+        MODE_Z[k]     t_k / sqrt(lam_k / (S - 1) (1 + 1 / S)): the error of the mean along mode k in units of the spread along it (the
+                      factor 1 + 1/S is the mean's own sampling variance)
+        MODE_Z_RMS    the root mean square of MODE_Z over the live modes: near 1 the spread along the ensemble's own modes matches the
+                      error, above 1 the ensemble is under-dispersed
+        rank, sweeps, valid, invalid
+    Lists over modes have length S, NaN at the dead modes; the target's keys are NaN without one; an image of rank 0 (S = 1, no valid
+    pixel, equal members) has NaN scores but SPAN_SHARE = 0 when the mean is in error; an image the kernel refused (rank -1: a NaN,
+    infinite or negative distance) is NaN throughout and is left out of the pooled record, which counts it in 'refused'.
+    'pooled' treats the images as one: the spectra are added mode by mode (sum over images of lam_k where live) and EXPLAINED, EFF_MODES
+    and MODE_STD are read off the sum, the latter with the pooled valid pixels; SPAN_SHARE = sum of all live t_k^2 / sum of tnorm2;
+    MODE_Z_RMS is over all images' live modes.
+    Caveat: at small S the leading sample eigenvalues are biased upward (and the trailing ones downward), so the leading MODE_Z are
+    biased low and EFF_MODES is an underestimate; compare ensembles at equal S.
+    -> dict(key -> the list over images, 'pooled' -> dict).  Takes tensors, arrays or nested lists."""
+    S = _num_samples(S)
+    lam = torch.as_tensor(lam, dtype=torch.float64).detach().cpu().reshape(-1, S).tolist()
+    tcoord = torch.as_tensor(tcoord, dtype=torch.float64).detach().cpu().reshape(-1, S).tolist()
+    tnorm2 = torch.as_tensor(tnorm2, dtype=torch.float64).detach().cpu().reshape(-1).tolist()
+    info = torch.as_tensor(info).detach().cpu().to(torch.int64).reshape(-1, 2).tolist()
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, 2).tolist()
+    if not len(lam) == len(tcoord) == len(tnorm2) == len(info) == len(counts):
+        raise ValueError(f"ensemble_mode_summary: {len(lam)} spectra, {len(tcoord)} rows of coordinates, {len(tnorm2)} norms, {len(info)} rows "
+                         f"of info, {len(counts)} rows of counts")
+    has_target = bool(has_target)
+    nan = float("nan")
+    keys = ("EXPLAINED", "EFF_MODES", "MODE_STD", "SPAN_SHARE", "MODE_Z", "MODE_Z_RMS", "rank", "sweeps", "valid", "invalid")
+    out = {k: [] for k in keys}
+    pool_lam, pool_t2, pool_n2, pool_z2, pool_nz, pool_valid, pool_invalid, refused = [0.0] * S, 0.0, 0.0, 0.0, 0, 0, 0, 0
+    for l, t, n2, (rank, sweeps), (valid, invalid) in zip(lam, tcoord, tnorm2, info, counts):
+        if rank < 0:
+            one = _mode_record([], [], nan, 0, S, False)
+            refused += 1
+        else:
+            rank = min(rank, S)
+            one = _mode_record(l[:rank], t[:rank], n2, valid, S, has_target)
+            if has_target and S > 1 and rank > 0:
+                z2 = sum(z * z for z in one["MODE_Z"][:rank])
+                one["MODE_Z_RMS"] = math.sqrt(z2 / rank)
+                pool_z2 += z2
+                pool_nz += rank
+            for k in range(rank):
+                pool_lam[k] += l[k]
+                pool_t2 += t[k] * t[k]
+            pool_n2 += n2
+            pool_valid += valid
+            pool_invalid += invalid
+        one.update(rank=rank, sweeps=sweeps, valid=valid, invalid=invalid)
+        for k in keys:
+            out[k].append(one[k])
+    live = 0
+    while live < S and pool_lam[live] > 0:
+        live += 1
+    pooled = _mode_record(pool_lam[:live], [], 0.0, pool_valid, S, False)
+    if has_target:
+        if pool_n2 > 0:
+            pooled["SPAN_SHARE"] = pool_t2 / pool_n2
+        if pool_nz:
+            pooled["MODE_Z_RMS"] = math.sqrt(pool_z2 / pool_nz)
+    del pooled["MODE_Z"]
+    pooled.update(images=len(lam) - refused, refused=refused, valid=pool_valid, invalid=pool_invalid)
+    out["pooled"] = pooled
+    return out
+
+
 def calibration_grid(lam_max=8.0, G=513):
     """The table of scale factors a calibration searches: lam_g = g * lam_max / (G - 1), g = 0 .. G - 1, computed in double and rounded
     to float32, as a list of G floats (each a float32 value).  2 <= G <= 1024, lam_max finite and > 0; refused if the rounded table is
@@ -1511,6 +1606,30 @@ class driftSDE:
             raise ValueError(f"member_distances: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
                              f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
         return ops.ensemble_distances(samples.contiguous(), None if target is None else target.contiguous())
+
+    @staticmethod
+    def principal_modes(samples, target=None, K=4):
+        """The principal components of samples [B, S, ...] (reverse_ddpm_ensemble(..., return_samples=True)) about their per-pixel mean,
+        with target [B, ...] placed in them when given -> dict(modes float32 [B, min(K, S), ...]: the leading unit-norm mode images
+        u_k; lam float64 [B, S]: the variance sums along the modes, descending; vec float64 [B, S, S]: row k = the members'
+        coordinates along u_k divided by sqrt(lam_k); tcoord float64 [B, S] = <target - mean, u_k>; tnorm2 float64 [B] =
+        |target - mean|^2; info int32 [B, 2] = (rank, sweeps); counts int32 [B, 2] = (valid, invalid) pixels), all on the device.
+        One ops.ensemble_distances call, one ops.ensemble_modes call and one ops.ensemble_project call (four launches for K <= 8), no
+        host copy; ensemble_mode_summary(lam, tcoord, tnorm2, info, counts, S, target is not None) reads EXPLAINED / EFF_MODES /
+        SPAN_SHARE / MODE_Z off them.  A member is mean + sum_k sqrt(lam_k) vec[k][s] u_k; a mode past the rank is a zero image."""
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError(f"principal_modes: K must be an int >= 1, got {K!r}")
+        if not torch.is_tensor(samples) or samples.dim() < 3:
+            raise ValueError("principal_modes: samples must be a [B, S, ...] tensor (reverse_ddpm_ensemble(..., return_samples=True))")
+        if target is not None and (not torch.is_tensor(target) or tuple(target.shape) != (samples.shape[0],) + tuple(samples.shape[2:])):
+            raise ValueError(f"principal_modes: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+        samples = samples.contiguous()
+        S = samples.shape[1]
+        d2, counts, _ = ops.ensemble_distances(samples, None if target is None else target.contiguous())
+        lam, vec, coef, tcoord, tnorm2, info = ops.ensemble_modes(d2, S, target is not None)
+        modes = ops.ensemble_project(samples, coef[:, :min(K, S)])
+        return dict(modes=modes, lam=lam, vec=vec, tcoord=tcoord, tnorm2=tnorm2, info=info, counts=counts)
 
     @staticmethod
     def power_spectra(samples_or_output, target=None):

@@ -267,6 +267,7 @@ class CLIPDriftModel():
         sde.interval set as well, output_median / output_lo / output_hi are the per-pixel median and credible-interval maps (else None)"""
         self.output_std = self.samples = None
         self.output_median = self.output_lo = self.output_hi = None
+        self.output_modes = None
         if getattr(self.sde, "num_samples", 1) > 1:
             res = self.sde.reverse_ddpm_ensemble(self.input, self.names, self.text_encoder, reverse_type=self.optimize_target,
                                                  optimize_type=self.optimize_type, image_context=self.A_emb, **kw)
@@ -313,6 +314,41 @@ class CLIPDriftModel():
             held = self._member_pick
         from .. import ops
         return ops.ensemble_pick_rows(self.samples.contiguous(), held[2], 0 if which == "medoid" else 1)
+
+    def principal_modes(self, K=4, with_target=True):
+        """the principal modes of the members test(return_samples=True) left in self.samples, with self.target placed in them when
+        with_target (driftSDE.principal_modes) -> dict(modes, lam, vec, tcoord, tnorm2, info, counts) on the device.  The mode images
+        are kept as self.output_modes [B, min(K, S), C, H, W], the record for mode_traversal."""
+        if getattr(self, "samples", None) is None:
+            raise ValueError("principal_modes: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        rec = self.sde.principal_modes(self.samples, self.target if with_target else None, K=K)
+        self.output_modes = rec["modes"]
+        self._modes = (self.samples, rec)
+        return rec
+
+    def mode_traversal(self, k, alpha):
+        """self.output moved along mode k by alpha standard deviations of the ensemble -> [B, C, H, W]:
+        output + alpha sqrt(lam_k / (S - 1)) u_k, one ops.axpby per image (the per-image scalar costs one small host read of lam).
+        Needs principal_modes(K > k) for the held samples; without such a call it is made first, without the target."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise ValueError(f"mode_traversal: k must be an int >= 0, got {k!r}")
+        if getattr(self, "samples", None) is None:
+            raise ValueError("mode_traversal: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+        S = self.samples.shape[1]
+        if k >= S:
+            raise ValueError(f"mode_traversal: k = {k} is outside the {S} modes of {S} members")
+        held = getattr(self, "_modes", None)
+        if held is None or held[0] is not self.samples or held[1]["modes"].shape[1] <= k:
+            self.principal_modes(K=max(k + 1, 4), with_target=False)
+            held = self._modes
+        from .. import ops
+        rec = held[1]
+        lam_k = rec["lam"][:, k].cpu().tolist()
+        out = torch.empty_like(self.output)
+        for b, l in enumerate(lam_k):
+            scale = float(alpha) * (l / (S - 1)) ** 0.5 if l > 0 else 0.0
+            ops.axpby(self.output[b].contiguous(), rec["modes"][b, k], 1.0, scale, out=out[b])
+        return out
 
     def sparsification(self, K=20, key="std"):
         """sparsification records of an uncertainty map of the ensemble test(return_samples=True) left, for self.output against

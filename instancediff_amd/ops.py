@@ -1004,6 +1004,74 @@ def ensemble_pick_rows(x, pick, col):
     return out
 
 
+ENSEMBLE_MODES_REL_FLOOR = 2.0 ** -30
+ENSEMBLE_PROJECT_MAX_K = 8
+
+
+def ensemble_modes(d2, S, has_target, rel_floor=ENSEMBLE_MODES_REL_FLOOR):
+    """d2 float64 [B, M, M] on the device (ops.ensemble_distances' matrix, M = S + has_target) -> (lam [B, S], vec [B, S, S], coef
+    [B, S, S], tcoord [B, S], tnorm2 [B], all float64, info int32 [B, 2] = rank, sweeps), all on the device: the principal modes of the
+    S members about their centroid.  lam are the eigenvalues of the centred Gram matrix in descending order, row k of vec the unit
+    eigenvector of lam[k], row k of coef = vec[k] / sqrt(lam[k]) (zeros for a mode at or below rel_floor * lam[0]), so that
+    ops.ensemble_project(x, coef[:, :K]) gives the K leading unit-norm mode images; with a target tcoord[k] is the coordinate of
+    (target - ensemble mean) along mode k and tnorm2 its squared norm.  One launch, no host copy; include/idiff.h states the centring,
+    the Jacobi schedule, the stop rule and the degenerate cases.  models/SDEs/driftSDE.py's ensemble_mode_summary reads EXPLAINED /
+    EFF_MODES / SPAN_SHARE / MODE_Z off them."""
+    lib = _lib.load()
+    _c(d2, "d2", torch.float64)
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise _lib.IdiffError(f"ensemble_modes: S must be an int >= 1, got {S!r}")
+    M = S + (1 if has_target else 0)
+    assert d2.dim() == 3 and tuple(d2.shape[1:]) == (M, M), f"ensemble_modes: d2 is [B, {M}, {M}], got {tuple(d2.shape)}"
+    B = d2.shape[0]
+    dev = d2.device
+    lam = torch.empty((B, S), device=dev, dtype=torch.float64)
+    vec = torch.empty((B, S, S), device=dev, dtype=torch.float64)
+    coef = torch.empty((B, S, S), device=dev, dtype=torch.float64)
+    tcoord = torch.empty((B, S), device=dev, dtype=torch.float64)
+    tnorm2 = torch.empty((B,), device=dev, dtype=torch.float64)
+    info = torch.empty((B, 2), device=dev, dtype=torch.int32)
+    check(lib.idiff_ensemble_modes(_p(d2), B, S, int(bool(has_target)), float(rel_floor), _p(lam), _p(vec), _p(coef), _p(tcoord), _p(tnorm2),
+                                   _p(info), _stream()), "ensemble_modes")
+    return lam, vec, coef, tcoord, tnorm2, info
+
+
+def ensemble_project(x, coef):
+    """x [B, S, ...] float32, coef [B, K, S] float64 on the device, any K >= 1 -> [B, K, ...] float32: plane k of image b is
+    sum_s coef[b, k, s] (x[b, s] - the per-pixel member mean), in fp64 per pixel with the members in index order; any coefficients are
+    taken (rows of ops.ensemble_modes' coef give unit-norm mode images).  A pixel where a member is NaN or infinite is NaN in every
+    plane.  One launch per ENSEMBLE_PROJECT_MAX_K rows of coef, no host copy."""
+    lib = _lib.load()
+    _c(x, "x"), _chk(coef, "coef", torch.float64)
+    assert x.dim() >= 3, "ensemble_project: x is [B, S, ...]"
+    B, S = x.shape[:2]
+    assert coef.dim() == 3 and coef.shape[0] == B and coef.shape[2] == S and coef.shape[1] >= 1, \
+        f"ensemble_project: coef is [B, K, S] = [{B}, K >= 1, {S}], got {tuple(coef.shape)}"
+    K = coef.shape[1]
+    if not coef.is_contiguous():  # the leading rows of a larger table (coef[:, :K] of ops.ensemble_modes) are read in place
+        if coef[0].is_contiguous() and coef.stride(0) >= K * S:
+            image_stride = coef.stride(0)
+        else:
+            raise _lib.IdiffError("coef must be contiguous, or contiguous [K, S] tables at a fixed distance")
+    else:
+        image_stride = K * S
+    n_s = x.numel() // (B * S) if B * S else 0
+    step = ENSEMBLE_PROJECT_MAX_K
+    direct = K <= step or B == 1  # the kernel writes [B][rows][n_s] densely: more than one chunk of a batch goes through pieces
+    out = torch.empty((B, K) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32) if direct else None
+    pieces = []
+    for k0 in range(0, K, step):
+        rows = min(step, K - k0)
+        if direct:
+            dst = out.data_ptr() + 4 * k0 * n_s
+        else:
+            pieces.append(torch.empty((B, rows) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32))
+            dst = pieces[-1].data_ptr()
+        check(lib.idiff_ensemble_project(_p(x), C.c_void_p(coef.data_ptr() + 8 * k0 * S), image_stride, C.c_void_p(dst), B, S, rows, n_s, _stream()),
+              "ensemble_project")
+    return out if direct else torch.cat(pieces, dim=1)
+
+
 SPARSIFICATION_MAX_K = 64
 
 

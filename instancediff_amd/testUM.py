@@ -23,6 +23,10 @@ With `--sparsification [K]` on top of `--num-samples S` the std map is tested as
 sort: per image `AUSE` (the area between the map's sparsification curve and the oracle's: 0 is a perfect ranking), `AURG` (the area gained over
 removal in random order: <= 0 is no better than chance) and `AUSE_RMSE` are listed for K points (default 20), per artifact type the pooled values
 are printed and the pooled curves (mean squared errors on RMSE's x/2 + 0.5 scale) go to `sparsification.json`.
+With `--modes [K]` on top of `--num-samples S` the members' joint variation is decomposed into principal modes on the device: per image `EFF_MODES`
+(the participation ratio of the spectrum: how many degrees of freedom the ensemble has), `EXPLAINED_1` (the leading mode's share of the variance),
+`SPAN_SHARE` (the share of the mean's squared error inside the members' span) and `MODE_Z_RMS` (error over spread along the modes: above 1 is
+under-dispersed) are listed, the K leading unit-norm mode images (default 4) go to `<i>_modes_WxHxK.raw`, the pooled values per artifact type to `modes.json`.
 With `--tile P [P]` / `--tile-overlap O` (driftSDE) an image larger than the window is restored as a batch of overlapping windows of one
 full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ensemble of tiled chains).  With `--reuse-graph` (driftSDE) the captured step graph is kept and replayed for every later image of the same shape.
 With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
@@ -43,7 +47,8 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import ensemble_distance_summary, ensemble_score_summary, sparsification_summary, spectrum_summary
+from .models.SDEs.driftSDE import (ensemble_distance_summary, ensemble_mode_summary, ensemble_score_summary, sparsification_summary,
+                                   spectrum_summary)
 
 
 def pool_spectra(entries, S):
@@ -110,7 +115,15 @@ def build_parser():
                         help="sparsification curves of the std map over K points, default 20 (needs num_samples > 1): AUSE / AURG / AUSE_RMSE "
                              "per image, the pooled values and sparsification.json per artifact type; an image whose C*H*W is not a "
                              "multiple of 4 is left out of the curves, with a note on its line")
+    # absent from the namespace without the flag, like --sparsification
+    parser.add_argument("--modes", type=int, nargs="?", const=4, default=argparse.SUPPRESS, metavar="K",
+                        help="principal modes of the ensemble, the K leading ones as images, default 4 (needs num_samples > 1): EFF_MODES / "
+                             "EXPLAINED_1 / SPAN_SHARE / MODE_Z_RMS per image, the pooled values and modes.json per artifact type; an image "
+                             "whose C*H*W is not a multiple of 4 is left out, with a note on its line")
     return parser
+
+
+MODES_MAX_K = 64  # the members of the largest ensemble the kernels take
 
 
 def main(argv=None):
@@ -132,6 +145,13 @@ def main(argv=None):
         if not isinstance(num, int) or num <= 1:
             parser.error("--sparsification ranks the pixels by an ensemble's spread: it needs num_samples > 1 (--num-samples S or the YAML's "
                          "num_samples)")
+    K_modes = getattr(args, "modes", None)
+    if K_modes is not None:  # refused before the model is built, like --sparsification
+        if not 1 <= K_modes <= MODES_MAX_K:
+            parser.error(f"--modes takes K in [1, {MODES_MAX_K}]")
+        num = yaml_num_samples(args, opt)
+        if not isinstance(num, int) or num <= 1:
+            parser.error("--modes decomposes the spread of an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
     rank, world, local = parallel.init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local if world > 1 else opt['gpu_ids'][0])
@@ -197,6 +217,9 @@ def main(argv=None):
     if K_sp is not None:
         for r in results.values():
             r['AUSE'], r['AURG'], r['AUSE_RMSE'], r['sparsification'] = [], [], [], []
+    if K_modes is not None:
+        for r in results.values():
+            r['EFF_MODES'], r['EXPLAINED_1'], r['SPAN_SHARE'], r['MODE_Z_RMS'], r['modes'] = [], [], [], [], []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -288,6 +311,19 @@ def main(argv=None):
                     r['sparsification'].append(rec)
                     r['AUSE'].append(one['AUSE']), r['AURG'].append(one['AURG']), r['AUSE_RMSE'].append(one['AUSE_RMSE'])
                     extra += f", AUSE={r['AUSE'][-1]}, AURG={r['AURG'][-1]}, AUSE_RMSE={r['AUSE_RMSE'][-1]}"
+                if K_modes is not None and model.output[0].numel() % 4:  # the kernels read 16-byte pieces
+                    extra += ", EFF_MODES=left out (C*H*W is not a multiple of 4)"
+                elif K_modes is not None:  # ratios and unit-norm images: no scale to carry
+                    rec = model.principal_modes(K=K_modes)
+                    host = [rec[q].cpu() for q in ('lam', 'tcoord', 'tnorm2', 'info', 'counts')]
+                    one = ensemble_mode_summary(*host, S, True)
+                    r['modes'].append(host)
+                    r['EFF_MODES'].append(one['EFF_MODES'][0]), r['EXPLAINED_1'].append(one['EXPLAINED'][0][0])
+                    r['SPAN_SHARE'].append(one['SPAN_SHARE'][0]), r['MODE_Z_RMS'].append(one['MODE_Z_RMS'][0])
+                    m = rec['modes'][0, :, 0].cpu()
+                    m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_modes_{m.shape[-1]}x{m.shape[-2]}x{m.shape[0]}.raw"))
+                    extra += (f", EFF_MODES={r['EFF_MODES'][-1]}, EXPLAINED_1={r['EXPLAINED_1'][-1]}, SPAN_SHARE={r['SPAN_SHARE'][-1]}, "
+                              f"MODE_Z_RMS={r['MODE_Z_RMS'][-1]}")
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -317,6 +353,16 @@ def main(argv=None):
                 json.dump(dict(S=S, K=K_sp, fractions=pooled['fractions'], curve=[0.25 * c for c in pooled['curve']],
                                oracle=[0.25 * c for c in pooled['oracle']], random=[0.25 * c for c in pooled['random']], AUSE=pooled['AUSE'],
                                AURG=pooled['AURG'], N=pooled['N'], invalid=pooled['invalid']), f)
+    if K_modes is not None:  # the type's record: the spectra added mode by mode over its images, not the mean of the per-image ratios
+        for k, v in results.items():
+            if not v['num'] or not v['modes']:
+                continue
+            pooled = ensemble_mode_summary(*(torch.cat([rec[q].reshape(1, -1) for rec in v['modes']]) for q in range(5)), S, True)['pooled']
+            v['pooled_modes'] = pooled
+            print(f"{k}, modes pooled over {len(v['modes'])} images: EFF_MODES: {pooled['EFF_MODES']}, EXPLAINED_1: {pooled['EXPLAINED'][0]}, "
+                  f"SPAN_SHARE: {pooled['SPAN_SHARE']}, MODE_Z_RMS: {pooled['MODE_Z_RMS']}, refused: {pooled['refused']}")
+            with open(os.path.join(result_root, k, "modes.json"), "w") as f:
+                json.dump(dict(S=S, K=min(K_modes, S), **pooled), f)
     if args.spectra:  # the type's record: the power sums pooled over its images, not the mean of the per-image ratios; per image size
         for k, v in results.items():
             v['pooled_spectra'] = pool_spectra(v.get('spectra', []), S)
