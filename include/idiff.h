@@ -720,6 +720,38 @@ int64_t idiff_radial_power_spectrum_ws_bytes(int R, int H, int W);
 int idiff_sparsification(const float* key, const float* pred, const float* target, int K, double* sums, int32_t* counts, float* tau, void* ws,
                          int B, int64_t n_s, idiff_stream_t stream);
 int64_t idiff_sparsification_ws_bytes(int B, int K, int64_t n_s);
+/* Region-wise ensemble scores: x [B][S][n_s], target [B][n_s], labels uint8 [B][n_s] (labels_bstride = n_s) or one map
+ * [n_s] shared by every image (labels_bstride = 0) -> idiff_ensemble_scores' record per region l = 0 .. L-1 of the label map.  The per-pixel
+ * arithmetic is that function's contract word for word (d_s, the ranks with their tie rule, a, g, crps, m, e = m*m, v, k: every operation
+ * rounded once in fp32, no contraction; a pixel is invalid if any d_s is NaN, infinite values are values); the fourth quantity is the
+ * signed m itself, the mean error of the members (the region's bias).  For S = 1: crps = |d|, e = d*d, v = 0, k in {0, 1}.
+ *   sums    float64 [B][L][4]     = sum crps, sum e, sum v, sum m over the valid pixels of region l
+ *   counts  int32 [B][L][S + 2]   = hist[0 .. S] of region l (its valid pixels per k), then its invalid pixels
+ *   outside int32 [B]             = the pixels whose label is >= L (255 is the conventional "ignore"); such a pixel adds nowhere else
+ *   ws      idiff_region_scores_ws_bytes(B, S, L) bytes, 8-byte aligned
+ * A label is compared against L before it is used: an out-of-range label never becomes an index.  Per image sum_l (hist + invalid) +
+ * outside = n_s.
+ * Two launches on idiff_ensemble_scores' order: a grid of (64, B) blocks of 256 threads; thread (p, tid) takes float4 p*256 + tid +
+ * i*16384 in sweep i, with its four labels as one 32-bit load; every lane runs all ceil(n_s / 65536) sweeps (a lane past the end adds
+ * nothing).  Per sweep and wave: the set of labels < L carried by a valid pixel of the wave, ascending; for each of them and each
+ * quantity a lane contributes the fp64 sum of (double)term over its elements 0 .. 3 that are valid and carry the label, in element order
+ * from +0.0; the wave adds these with the fixed xor tree (offsets 32, 16, .. 1); the wave's sum is added to the wave's slot [label]
+ * [quantity] in sweep order; at the end the four waves' slots are added in wave order: one fp64 partial per block, label and quantity.
+ * The second launch adds an image's 64 partials in index order.  Histograms are L (S + 2) int32 bins in LDS (integer LDS adds).  No float
+ * atomics, no global atomics: the record of image b depends on neither B nor the run; with L = 1 and no outside label, sums[.][0][0..2]
+ * carry idiff_ensemble_scores' bits for n_s <= 65536.  For S <= 16 a thread keeps its S float4 in registers; above that (or with
+ * IDIFF_ENSEMBLE_REREAD=1 in the environment) it reads the members again; the bits are the same.
+ * 1 <= S <= 64, 1 <= L <= 64, n_s % 4 == 0, n_s < 2^31, 1 <= B <= 65535; x / target 16-byte aligned, labels 4-byte aligned, labels_bstride
+ * 0 or n_s, sums / ws 8-byte aligned; sums, counts, outside and ws overlap neither each other nor the inputs.  A refused call
+ * (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_region_scores(const float* x, const float* target, const uint8_t* labels, int64_t labels_bstride, int L, double* sums,
+                        int32_t* counts, int32_t* outside, void* ws, int B, int S, int64_t n_s, idiff_stream_t stream);
+int64_t idiff_region_scores_ws_bytes(int B, int S, int L);
+/* Intensity-band labels for idiff_region_scores: labels[i] = #{ j : edges[j] <= y[i] } (np.searchsorted(edges, y, side="right")), 255
+ * where y[i] is NaN; -inf gives 0 and +inf gives ne.  1 <= ne <= 63 host floats, finite and strictly ascending, passed to the kernel by
+ * value (no device table).  One launch, a thread takes 16 pixels (four 16-byte loads, one 16-byte store); a last piece shorter than
+ * 16 goes element by element.  n >= 1, y and labels 16-byte aligned and not overlapping.  A refused call leaves labels untouched. */
+int idiff_band_labels(const float* y, uint8_t* labels, int64_t n, const float* edges_host, int ne, idiff_stream_t stream);
 /* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
  * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
  * the flips applied after the transposition:

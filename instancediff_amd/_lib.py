@@ -146,6 +146,9 @@ SIGNATURES = {
     "idiff_radial_power_spectrum_ws_bytes": (I64, [I, I, I]),
     "idiff_sparsification": (I, [P, P, P, I, P, P, P, P, I, I64, c_stream]),
     "idiff_sparsification_ws_bytes": (I64, [I, I, I64]),
+    "idiff_region_scores": (I, [P, P, P, I64, I, P, P, P, P, I, I, I64, c_stream]),
+    "idiff_region_scores_ws_bytes": (I64, [I, I, I]),
+    "idiff_band_labels": (I, [P, P, I64, C.POINTER(C.c_float), I, c_stream]),
     "idiff_dihedral_rows": (I, [P, P, I, I, I, I, I, I, I, C.c_uint32, c_stream]),
     "idiff_tile_gather": (I, [P, P, I, I, I, I, I, I, I, I, P, P, c_stream]),
     "idiff_drift_reverse_step_tiled_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, U64, U64, U64, c_stream]),

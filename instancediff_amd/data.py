@@ -45,7 +45,13 @@ class SpeckleMedDataset:
             A, B = A.clamp(0, 1800) / 1800.0, B.clamp(0, 1800) / 1800.0
         if name == "noise in cryo-EM image":
             A, B = A.clamp(0.0, 255.0) / 255.0, B.clamp(0.0, 255.0) / 255.0
-        return {"LQ": A * 2.0 - 1.0, "GT": B * 2.0 - 1.0, "LQ_path": it["A"], "GT_path": it["B"], "name": name, "A_emb": A_emb}
+        out = {"LQ": A * 2.0 - 1.0, "GT": B * 2.0 - 1.0, "LQ_path": it["A"], "GT_path": it["B"], "name": name, "A_emb": A_emb}
+        if "label" in it:  # optional: a raw uint8 label map of the image's size (testUM --regions file); items without it are as before
+            lab = np.fromfile(it["label"], dtype=np.uint8)
+            if lab.size != B[0].numel():
+                raise ValueError(f"{it['label']}: {lab.size} labels for an image of {B[0].numel()} pixels")
+            out["LABEL"] = torch.from_numpy(lab.reshape(tuple(B.shape[1:])).copy())
+        return out
 
 
 class SyntheticDataset:

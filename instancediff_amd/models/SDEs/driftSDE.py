@@ -200,6 +200,68 @@ def ensemble_score_summary(sums, counts, S):
                 hist=hist, invalid=invalid)
 
 
+def _region_record(tot, pooled, S, err_total, pix_total, data_range):
+    """one region's scores from its (pooled) four sums and S + 2 counts; every quotient is None without a valid pixel"""
+    hist, invalid = pooled[:S + 1], pooled[S + 1]
+    N = sum(hist)
+    rec = dict(N_PIX=N, CRPS=None, RMSE=None, PSNR=None, BIAS=None, SSR=None, RANK_DEV=None, OUTLIERS=None, ERR_SHARE=None,
+               PIX_SHARE=N / pix_total if pix_total else None, hist=hist, invalid=invalid)
+    if N == 0:
+        return rec
+    skill = math.sqrt(tot[1] / N) if tot[1] >= 0 else float("nan")
+    rec.update(CRPS=tot[0] / N, RMSE=skill, BIAS=tot[3] / N, PSNR=20.0 * math.log10(data_range / skill) if skill > 0 and math.isfinite(skill) else None,
+               ERR_SHARE=tot[1] / err_total if err_total > 0 and math.isfinite(err_total) else None)
+    if S > 1:
+        spread = math.sqrt((S + 1) / S * tot[2] / N) if tot[2] >= 0 else float("nan")
+        rec.update(SSR=spread / skill if skill > 0 else None, RANK_DEV=sum(abs(h / N - 1.0 / (S + 1)) for h in hist),
+                   OUTLIERS=(hist[0] + hist[S]) / N)
+    return rec
+
+
+def region_score_summary(sums, counts, outside, S, names=None, data_range=2.0):
+    """The per-region scores of N images from what ops.region_scores returns, on the host:
+        sums [N, L, 4] = sum crps, sum e, sum v, sum m per region;  counts [N, L, S + 2] = the region's rank histogram hist[0..S], then
+        its invalid pixels;  outside [N] = the pixels of no region.
+    Images are pooled before dividing, sums with sums and bins with bins, as in ensemble_score_summary.  ->  dict(S, L, names,
+        regions   one dict per region, pooled over the images:
+            N_PIX      sum hist: the region's valid pixels
+            CRPS       sum crps / N_PIX (the MAE for S = 1)
+            RMSE       sqrt(sum e / N_PIX), of the ensemble mean;  PSNR = 20 log10(data_range / RMSE), None for RMSE = 0
+            BIAS       sum m / N_PIX: the signed mean error
+            SSR, RANK_DEV, OUTLIERS   exactly ensemble_score_summary's; None for S = 1
+            ERR_SHARE  the region's sum e over all regions' sum e;  PIX_SHARE  its N_PIX over all regions' N_PIX
+            hist, invalid
+        images    the same list per image
+        N_PIX, invalid, outside   the totals)
+    A region without a valid pixel has None in every quotient: nothing divides by zero.  data_range is that of the tensors scored
+    ([-1, 1]: 2).  names: L strings for the regions, default "0" .. "L-1".  Takes tensors, arrays or nested lists."""
+    S = _num_samples(S)
+    sums = torch.as_tensor(sums, dtype=torch.float64).detach().cpu()
+    if sums.dim() < 2 or sums.shape[-1] != 4:
+        raise ValueError(f"region_score_summary: sums must be [N, L, 4] or [L, 4], got {tuple(sums.shape)}")
+    L = int(sums.shape[-2])
+    sums = sums.reshape(-1, L, 4)
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(-1, L, S + 2)
+    outside = torch.as_tensor(outside).detach().cpu().to(torch.int64).reshape(-1)
+    if not sums.shape[0] == counts.shape[0] == outside.shape[0]:
+        raise ValueError(f"region_score_summary: {sums.shape[0]} rows of sums, {counts.shape[0]} of counts, {outside.shape[0]} of outside")
+    names = [str(i) for i in range(L)] if names is None else [str(n) for n in names]
+    if len(names) != L:
+        raise ValueError(f"region_score_summary: {len(names)} names for L = {L} regions")
+    if not data_range > 0:
+        raise ValueError(f"region_score_summary: data_range must be > 0, got {data_range!r}")
+
+    def table(s, c):  # s [L][4], c [L][S + 2] as lists
+        err_total = sum(s[l][1] for l in range(L) if sum(c[l][:S + 1]) > 0)
+        pix_total = sum(sum(c[l][:S + 1]) for l in range(L))
+        return [dict(name=names[l], **_region_record(s[l], c[l], S, err_total, pix_total, data_range)) for l in range(L)]
+
+    regions = table(sums.sum(dim=0).tolist(), counts.sum(dim=0).tolist())
+    images = [table(s, c) for s, c in zip(sums.tolist(), counts.tolist())]
+    return dict(S=S, L=L, names=names, regions=regions, images=images, N_PIX=sum(r["N_PIX"] for r in regions),
+                invalid=sum(r["invalid"] for r in regions), outside=int(outside.sum()))
+
+
 def _sparsification_K(K):
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPARSIFICATION_MAX_K:
         raise ValueError(f"sparsification: K must be an int in [1, {ops.SPARSIFICATION_MAX_K}], got {K!r}")
@@ -1577,6 +1639,23 @@ class driftSDE:
             raise ValueError(f"score_ensemble: target must be [B, ...] = {(samples.shape[0],) + tuple(samples.shape[2:])}, got "
                              f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
         return ops.ensemble_scores(samples.contiguous(), target.contiguous(), want_map=want_map)
+
+    @staticmethod
+    def region_scores(samples_or_output, target, labels, L):
+        """The ensemble-scores record per region of a uint8 label map: samples [B, S, ...] (or one restoration [B, ...], S = 1) against
+        target [B, ...], labels [B, ...] or one shared [...] -> (sums float64 [B, L, 4], counts int32 [B, L, S + 2], outside int32 [B]) on
+        the device, from one ops.region_scores call (two launches, no host copy); region_score_summary(sums, counts, outside, S) reads
+        the per-region CRPS / RMSE / PSNR / BIAS / SSR / RANK_DEV / OUTLIERS and the error shares off them."""
+        x = samples_or_output
+        if not torch.is_tensor(target) or target.dim() < 2:
+            raise ValueError("region_scores: target must be a [B, ...] tensor")
+        want = (tuple(target.shape), tuple(target.shape[:1]) + (x.shape[1] if torch.is_tensor(x) and x.dim() > 1 else 0,) + tuple(target.shape[1:]))
+        if not torch.is_tensor(x) or tuple(x.shape) not in want:
+            raise ValueError(f"region_scores: samples must be [B, S, ...] or [B, ...] for target {tuple(target.shape)}, got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) not in (tuple(target.shape), tuple(target.shape[1:])):
+            raise ValueError(f"region_scores: labels must be a uint8 tensor of shape {tuple(target.shape)} or {tuple(target.shape[1:])}")
+        return ops.region_scores(x.contiguous(), target.contiguous(), labels.contiguous(), L)
 
     @staticmethod
     def sparsification(output, uncertainty, target, K=20):

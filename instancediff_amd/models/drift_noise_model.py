@@ -370,6 +370,33 @@ class CLIPDriftModel():
             unc = self.score_ensemble(want_map=True)[2]
         return self.sde.sparsification(self.output, unc, self.target, K=K)
 
+    def region_scores(self, labels, L, what="ensemble"):
+        """the ensemble-scores record per region of a uint8 label map, of what test() left against self.target (driftSDE.region_scores)
+        -> (sums [B, L, 4], counts [B, L, S + 2], outside [B]) on the device.  what: "ensemble", the members in self.samples (needs
+        test(return_samples=True)); "output", self.output as an ensemble of one (S = 1: MAE / RMSE / bias per region); "median",
+        output_median (needs the sde's interval).  labels: [B, C, H, W], one shared [C, H, W], or [H, W], which is expanded over the
+        channels; a label >= L (255 by convention) keeps its pixel out of every region."""
+        if what not in ("ensemble", "output", "median"):
+            raise ValueError(f'region_scores: what must be "ensemble", "output" or "median", got {what!r}')
+        if getattr(self, "output", None) is None:
+            raise ValueError("region_scores: no output is held; run test() first")
+        if what == "ensemble":
+            if getattr(self, "samples", None) is None:
+                raise ValueError("region_scores: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+            held = self.samples
+        elif what == "median":
+            if getattr(self, "output_median", None) is None:
+                raise ValueError("region_scores: no median map is held; run test(return_samples=True) with the sde's interval set first")
+            held = self.output_median
+        else:
+            held = self.output
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8:
+            raise ValueError("region_scores: labels must be a uint8 tensor")
+        labels = labels.to(self.target.device)
+        if labels.dim() == 2:
+            labels = labels[None].expand(self.target.shape[1], -1, -1)
+        return self.sde.region_scores(held, self.target, labels.contiguous(), L)
+
     def power_spectra(self, with_target=True):
         """radial power spectra of what test() left (driftSDE.power_spectra): of the members in self.samples and their mean after
         test(return_samples=True), else of self.output (the plain chain: S = 1), against self.target when with_target -> a dict of

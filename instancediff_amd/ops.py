@@ -1099,6 +1099,76 @@ def sparsification(key, pred, target, K=20):
     return sums, counts, tau
 
 
+REGION_MAX_L = 64
+REGION_MAX_S = 64
+BAND_MAX_EDGES = 63
+
+
+def region_scores(x, target, labels, L):
+    """x [B, S, ...] (the samples of an ensemble) or [B, ...] (one restoration, S = 1), target [B, ...], labels uint8 [B, ...] (one map
+    per image) or [...] (one map shared by every image), L regions -> (sums float64 [B, L, 4], counts int32 [B, L, S + 2], outside int32
+    [B]), all on the device: ops.ensemble_scores' record per region -- the sums of the per-pixel CRPS, squared error of the ensemble mean,
+    sample variance and signed mean error over the region's valid pixels; the region's rank histogram followed by its invalid pixels --
+    and the pixels whose label is >= L (255 is the conventional "ignore"), which add nowhere else.  Two launches, no host copy;
+    include/idiff.h states the arithmetic and the order.  models/SDEs/driftSDE.py's region_score_summary turns (pooled) records into
+    per-region CRPS / RMSE / PSNR / BIAS / SSR / RANK_DEV / OUTLIERS and the error shares."""
+    lib = _lib.load()
+    _c(x, "x"), _c(target, "target"), _c(labels, "labels", torch.uint8)
+    if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= REGION_MAX_L:
+        raise _lib.IdiffError(f"region_scores: L must be an int in [1, {REGION_MAX_L}], got {L!r}")
+    assert target.dim() >= 2, "region_scores: target is [B, ...]"
+    if x.dim() == target.dim():
+        x = x.unsqueeze(1)
+    B, S = x.shape[:2]
+    assert tuple(target.shape) == (B,) + tuple(x.shape[2:]), "region_scores: target is x without the member axis"
+    shared = tuple(labels.shape) == tuple(target.shape[1:])
+    assert shared or tuple(labels.shape) == tuple(target.shape), "region_scores: labels has the shape of target, or of one image of it"
+    n_s = x.numel() // (B * S) if B * S else 0
+    sums = torch.empty((B, L, 4), device=x.device, dtype=torch.float64)
+    counts = torch.empty((B, L, S + 2), device=x.device, dtype=torch.int32)
+    outside = torch.empty((B,), device=x.device, dtype=torch.int32)
+    ws = torch.empty((max(int(lib.idiff_region_scores_ws_bytes(B, S, L)), 8) // 8,), device=x.device, dtype=torch.float64)
+    check(lib.idiff_region_scores(_p(x), _p(target), _p(labels), 0 if shared else n_s, L, C.c_void_p(sums.data_ptr()),
+                                  C.c_void_p(counts.data_ptr()), C.c_void_p(outside.data_ptr()), C.c_void_p(ws.data_ptr()), B, S, n_s,
+                                  _stream()), "region_scores")
+    return sums, counts, outside
+
+
+def band_labels(target, edges):
+    """target (any shape, float32) -> uint8 labels of the same shape: labels = #{ j : edges[j] <= target }, i.e.
+    np.searchsorted(edges, target, side="right"), and 255 where target is NaN.  edges: 1 .. 63 finite, strictly ascending host floats
+    (rounded to float32), passed by value: "error by intensity band of the truth" for ops.region_scores with L = len(edges) + 1."""
+    lib = _lib.load()
+    _c(target, "target")
+    edges = [float(e) for e in edges]
+    ne = len(edges)
+    labels = torch.empty(target.shape, device=target.device, dtype=torch.uint8)
+    edges_host = (C.c_float * max(ne, 1))(*edges)
+    check(lib.idiff_band_labels(_p(target), _p(labels), target.numel(), edges_host, ne, _stream()), "band_labels")
+    return labels
+
+
+@functools.lru_cache(maxsize=16)
+def _grid_labels_host(H, W, gy, gx):
+    return torch.tensor([[(r * gy // H) * gx + (c * gx // W) for c in range(W)] for r in range(H)], dtype=torch.uint8)
+
+
+@functools.lru_cache(maxsize=16)
+def _grid_labels_dev(H, W, gy, gx, device):
+    return _grid_labels_host(H, W, gy, gx).to(device)
+
+
+def grid_labels(H, W, gy, gx, device="cpu"):
+    """uint8 [H, W] labels of a gy x gx grid of near-equal cells: label(r, c) = (r gy // H) gx + (c gx // W), gy gx <= 64 regions.
+    Built on the host in integer arithmetic and cached per (H, W, gy, gx, device): treat the tensor as read-only."""
+    for name, val in (("H", H), ("W", W), ("gy", gy), ("gx", gx)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"grid_labels: {name} must be an int >= 1, got {val!r}")
+    if gy * gx > REGION_MAX_L or gy > H or gx > W:
+        raise ValueError(f"grid_labels: a {gy} x {gx} grid needs gy gx <= {REGION_MAX_L}, gy <= H = {H} and gx <= W = {W}")
+    return _grid_labels_dev(H, W, gy, gx, str(torch.device(device)))
+
+
 @functools.lru_cache(maxsize=16)
 def radial_bins(H, W):
     """The radial frequency bins of an H x W image's half plane, on the host in exact integer arithmetic -> (bins int32 [H, Wh], counts

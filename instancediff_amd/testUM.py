@@ -32,10 +32,16 @@ full-resolution chain; `--tiled-ensemble` lets that meet `--num-samples` (an ens
 With `--self-ensemble {flips,dihedral}` on top of `--num-samples S` (driftSDE) the members also differ in orientation: each runs on a flipped /
 transposed copy of the image and is turned back before the mean, the maps and the scores (a geometric self-ensemble).
 With `--random-init` the checkpoint load
-is skipped (synthetic smoke runs).  Sampling shards by image across ranks when launched with torchrun.
+is skipped (synthetic smoke runs).
+With `--regions SPEC` the scores are also taken per region of a label map, on the device, with or without `--num-samples` (S = 1 scores the
+restoration itself): `bands:e1,e2,...` labels every pixel by the intensity band of its ground truth (edges on the x/2 + 0.5 scale),
+`grid:GYxGX` by the cell of a GY x GX grid, `file` by the raw uint8 map the dataset item's optional `"label"` key names (`--regions-L L`
+regions; any label >= L, 255 by convention, is outside).  Per image `RMSE_r`, `CRPS_r` (the MAE at S = 1), `BIAS_r` (x/2 + 0.5 scale) and
+`SSR_r` are listed region by region; the pooled record per artifact type goes to `regions.json`.  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
 import json
+import math
 import os
 import time
 from collections import OrderedDict
@@ -47,8 +53,8 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import (ensemble_distance_summary, ensemble_mode_summary, ensemble_score_summary, sparsification_summary,
-                                   spectrum_summary)
+from .models.SDEs.driftSDE import (ensemble_distance_summary, ensemble_mode_summary, ensemble_score_summary, region_score_summary,
+                                   sparsification_summary, spectrum_summary)
 
 
 def pool_spectra(entries, S):
@@ -120,10 +126,69 @@ def build_parser():
                         help="principal modes of the ensemble, the K leading ones as images, default 4 (needs num_samples > 1): EFF_MODES / "
                              "EXPLAINED_1 / SPAN_SHARE / MODE_Z_RMS per image, the pooled values and modes.json per artifact type; an image "
                              "whose C*H*W is not a multiple of 4 is left out, with a note on its line")
+    # absent from the namespace without the flags, like --sparsification
+    parser.add_argument("--regions", type=str, default=argparse.SUPPRESS, metavar="SPEC",
+                        help="per-region scores over a label map, with or without num_samples (S = 1 scores the restoration itself): "
+                             "bands:e1,e2,... (intensity bands of the ground truth, edges on the x/2 + 0.5 scale), grid:GYxGX (a grid of "
+                             "GY x GX cells, at most 64) or file (the raw uint8 map named by the dataset item's \"label\" key, with "
+                             "--regions-L); RMSE_r / CRPS_r / BIAS_r / SSR_r per image and regions.json per artifact type")
+    parser.add_argument("--regions-L", type=int, default=argparse.SUPPRESS, metavar="L", dest="regions_L",
+                        help="the number of regions of --regions file: labels 0 .. L-1 count, any other label (255 by convention) is outside")
     return parser
 
 
 MODES_MAX_K = 64  # the members of the largest ensemble the kernels take
+
+
+def parse_regions(spec, regions_L=None):
+    """--regions SPEC (and --regions-L) -> dict(kind, L, names, spec and, by kind, edges: the band edges on the tensors' [-1, 1] scale
+    as float32 values | gy, gx).  Raises ValueError with the message parser.error prints."""
+    kind, _, rest = str(spec).partition(":")
+    if kind != "file" and regions_L is not None:
+        raise ValueError("--regions-L goes with --regions file: bands and grids know their number of regions")
+    if kind == "bands":
+        try:
+            shown = [float(t) for t in rest.split(",")]
+        except ValueError:
+            raise ValueError(f"--regions bands: takes comma-separated numbers, got {rest!r}") from None
+        if not 1 <= len(shown) <= ops.BAND_MAX_EDGES:
+            raise ValueError(f"--regions bands: takes 1 to {ops.BAND_MAX_EDGES} edges, got {len(shown)}")
+        if not all(math.isfinite(e) for e in shown):
+            raise ValueError("--regions bands: the edges must be finite")
+        edges = torch.tensor([2.0 * e - 1.0 for e in shown], dtype=torch.float64).to(torch.float32).tolist()  # x/2 + 0.5 -> [-1, 1]
+        if any(b <= a for a, b in zip(edges, edges[1:])):
+            raise ValueError("--regions bands: the edges must be strictly ascending")
+        names = [f"<{shown[0]:g}"] + [f"{a:g}..{b:g}" for a, b in zip(shown, shown[1:])] + [f">={shown[-1]:g}"]
+        return dict(kind="bands", spec=str(spec), L=len(edges) + 1, names=names, edges=edges)
+    if kind == "grid":
+        parts = rest.lower().split("x")
+        if len(parts) != 2 or not all(p.isdigit() for p in parts):
+            raise ValueError(f"--regions grid: takes GYxGX, got {rest!r}")
+        gy, gx = int(parts[0]), int(parts[1])
+        if gy < 1 or gx < 1 or gy * gx > ops.REGION_MAX_L:
+            raise ValueError(f"--regions grid: GY and GX must be >= 1 with GY*GX <= {ops.REGION_MAX_L}, got {gy}x{gx}")
+        return dict(kind="grid", spec=str(spec), L=gy * gx, names=[f"r{y}c{x}" for y in range(gy) for x in range(gx)], gy=gy, gx=gx)
+    if kind == "file" and not rest:
+        if isinstance(regions_L, bool) or not isinstance(regions_L, int) or not 1 <= regions_L <= ops.REGION_MAX_L:
+            raise ValueError(f"--regions file: needs --regions-L L with L in [1, {ops.REGION_MAX_L}]")
+        return dict(kind="file", spec=str(spec), L=regions_L, names=[str(l) for l in range(regions_L)])
+    raise ValueError(f"--regions takes bands:e1,e2,..., grid:GYxGX or file, got {spec!r}")
+
+
+def region_labels(regions, model, item):
+    """the uint8 label map of one image for model.region_scores, by the kind of --regions"""
+    if regions["kind"] == "bands":
+        return ops.band_labels(model.target, regions["edges"])
+    if regions["kind"] == "grid":
+        H, W = (int(n) for n in model.target.shape[-2:])
+        return ops.grid_labels(H, W, regions["gy"], regions["gx"], str(model.target.device))
+    if "LABEL" not in item:
+        raise ValueError(f"--regions file: the dataset item of {item['GT_path']} has no \"label\" key")
+    return item["LABEL"]
+
+
+def _scaled(v, scale):
+    return None if v is None else scale * v
 
 
 def main(argv=None):
@@ -152,6 +217,14 @@ def main(argv=None):
         num = yaml_num_samples(args, opt)
         if not isinstance(num, int) or num <= 1:
             parser.error("--modes decomposes the spread of an ensemble: it needs num_samples > 1 (--num-samples S or the YAML's num_samples)")
+    regions = None
+    if hasattr(args, "regions") or hasattr(args, "regions_L"):  # refused before the model is built, like --sparsification
+        if not hasattr(args, "regions"):
+            parser.error("--regions-L goes with --regions file")
+        try:
+            regions = parse_regions(args.regions, getattr(args, "regions_L", None))
+        except ValueError as e:
+            parser.error(str(e))
     rank, world, local = parallel.init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local if world > 1 else opt['gpu_ids'][0])
@@ -220,6 +293,9 @@ def main(argv=None):
     if K_modes is not None:
         for r in results.values():
             r['EFF_MODES'], r['EXPLAINED_1'], r['SPAN_SHARE'], r['MODE_Z_RMS'], r['modes'] = [], [], [], [], []
+    if regions is not None:
+        for r in results.values():
+            r['regions'] = []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -324,6 +400,15 @@ def main(argv=None):
                     m.numpy().tofile(os.path.join(result_root, it["name"], f"{i}_modes_{m.shape[-1]}x{m.shape[-2]}x{m.shape[0]}.raw"))
                     extra += (f", EFF_MODES={r['EFF_MODES'][-1]}, EXPLAINED_1={r['EXPLAINED_1'][-1]}, SPAN_SHARE={r['SPAN_SHARE'][-1]}, "
                               f"MODE_Z_RMS={r['MODE_Z_RMS'][-1]}")
+                if regions is not None and model.output[0].numel() % 4:  # the kernel reads 16-byte pieces
+                    extra += ", RMSE_r=left out (C*H*W is not a multiple of 4)"
+                elif regions is not None:  # errors on RMSE's x/2 + 0.5 scale: half of what the [-1, 1] tensors give; SSR is a ratio
+                    rec = [t.cpu() for t in model.region_scores(region_labels(regions, model, it), regions["L"],
+                                                                what="ensemble" if S > 1 else "output")]
+                    one = region_score_summary(*rec, S, regions["names"])["regions"]
+                    r['regions'].append(rec)
+                    extra += (f", RMSE_r={[_scaled(q['RMSE'], 0.5) for q in one]}, CRPS_r={[_scaled(q['CRPS'], 0.5) for q in one]}, "
+                              f"BIAS_r={[_scaled(q['BIAS'], 0.5) for q in one]}, SSR_r={[q['SSR'] for q in one]}")
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -353,6 +438,22 @@ def main(argv=None):
                 json.dump(dict(S=S, K=K_sp, fractions=pooled['fractions'], curve=[0.25 * c for c in pooled['curve']],
                                oracle=[0.25 * c for c in pooled['oracle']], random=[0.25 * c for c in pooled['random']], AUSE=pooled['AUSE'],
                                AURG=pooled['AURG'], N=pooled['N'], invalid=pooled['invalid']), f)
+    if regions is not None:  # the type's record: sums and histograms pooled over its images region by region, then divided
+        for k, v in results.items():
+            if not v['num'] or not v['regions']:
+                continue
+            pooled = region_score_summary(*(torch.cat([rec[q] for rec in v['regions']]) for q in range(3)), S, regions["names"])
+            v['pooled_regions'] = pooled
+            for q in pooled["regions"]:
+                for tag in ("CRPS", "RMSE", "BIAS"):
+                    q[tag] = _scaled(q[tag], 0.5)
+            print(f"{k}, regions ({regions['spec']}) pooled over {len(v['regions'])} images: "
+                  + "; ".join(f"{q['name']}: N_PIX {q['N_PIX']}, RMSE {q['RMSE']}, CRPS {q['CRPS']}, BIAS {q['BIAS']}, SSR {q['SSR']}, ERR_SHARE "
+                              f"{q['ERR_SHARE']}, PIX_SHARE {q['PIX_SHARE']}" for q in pooled["regions"])
+                  + f"; invalid: {pooled['invalid']}, outside: {pooled['outside']}")
+            with open(os.path.join(result_root, k, "regions.json"), "w") as f:  # CRPS / RMSE / BIAS on RMSE's x/2 + 0.5 scale
+                json.dump(dict(spec=regions["spec"], S=S, L=pooled["L"], names=pooled["names"], images=len(v['regions']),
+                               regions=pooled["regions"], N_PIX=pooled["N_PIX"], invalid=pooled["invalid"], outside=pooled["outside"]), f)
     if K_modes is not None:  # the type's record: the spectra added mode by mode over its images, not the mean of the per-image ratios
         for k, v in results.items():
             if not v['num'] or not v['modes']:
