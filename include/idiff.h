@@ -752,6 +752,41 @@ int64_t idiff_region_scores_ws_bytes(int B, int S, int L);
  * value (no device table).  One launch, a thread takes 16 pixels (four 16-byte loads, one 16-byte store); a last piece shorter than
  * 16 goes element by element.  n >= 1, y and labels 16-byte aligned and not overlapping.  A refused call leaves labels untouched. */
 int idiff_band_labels(const float* y, uint8_t* labels, int64_t n, const float* edges_host, int ne, idiff_stream_t stream);
+/* No-reference despeckling statistics per region of a label map: x [B][S][P][H][W] (the restored rows; S = 1: one
+ * restoration), ref [B][P][H][W] (the noisy input, or the target where one exists), labels uint8 [B][P][H][W] (labels_bstride = P H W) or
+ * one map [P][H][W] shared by every image (labels_bstride = 0); row (b, s) uses ref[b] and labels[b].  Per pixel in fp32, every operation
+ * rounded once, no contraction:
+ *   a = x*scale + shift (a multiply, then an add), y likewise from ref; the pixel is valid iff a and y are both finite (unlike in
+ *   idiff_region_scores +-inf is invalid: the stencils subtract);
+ *   rho = y / a (correctly rounded), counted iff the pixel is valid and a >= ratio_floor;
+ *   La = ((a_N + a_S) + (a_W + a_E)) - 4*a, Ly likewise, counted iff the centre and its four neighbours lie in the same H x W plane and
+ *   all five are valid.  A stencil term belongs to the centre pixel's region: the neighbours' labels play no part, a neighbour with a
+ *   label >= L still lends its value.
+ *   sums    float64 [B][S][L][12] = sum a, a^2, y, y^2, a*y over the valid pixels of region l; sum rho, rho^2 over its ratio pixels;
+ *                                   sum La, Ly, La^2, Ly^2, La*Ly over its stencil pixels.  Each term is converted to double first and
+ *                                   the products are formed in double (exact: two fp32 factors), so only the summation rounds.
+ *   counts  int32 [B][S][L][4]    = the region's valid, ratio, stencil and invalid pixels
+ *   outside int32 [B]             = the pixels whose label is >= L (255 is the conventional "ignore"); such a pixel adds nowhere else
+ *   ws      idiff_despeckle_stats_ws_bytes(B, S, L) bytes, 8-byte aligned
+ * A label is compared against L before it is used: an out-of-range label never becomes an index.  Per row sum_l (valid + invalid) +
+ * outside = P H W.  H <= 2 leaves no stencil pixel: those counts are 0 and those sums +0.0.
+ * Two launches on idiff_region_scores' order: a grid of (64, B S) blocks of 256 threads; thread (p, tid) of a row takes the aligned
+ * float4 p*256 + tid + i*16384 of the row's P H W / 4 in sweep i (W % 4 == 0: a float4 never spans two lines), its four labels as one
+ * 32-bit load, its N / S neighbours as the aligned float4 one line up / down and the W / E neighbours of its end elements as two scalar
+ * loads, all from global memory and only where they lie in the centre's plane; every lane runs all ceil(P H W / 65536) sweeps (a lane
+ * past the end adds nothing).  Per sweep and wave: the set of labels < L carried by a valid pixel of the wave, ascending; for each of
+ * them and each quantity in the order above a lane contributes the fp64 sum of the terms of its elements 0 .. 3 that carry the label and
+ * count for the quantity, in element order from +0.0; the wave adds these with the fixed xor tree (offsets 32, 16, .. 1); the wave's sum
+ * is added to the wave's slot [label][quantity] in sweep order; at the end the four waves' slots are added in wave order: one fp64
+ * partial per block, label and quantity.  The second launch adds a row's 64 partials in index order.  Counts are L * 4 int32 in LDS
+ * (integer LDS adds).  No float atomics, no global atomics: the record of row (b, s) depends on neither B, S, the other rows nor the run.
+ * 1 <= S <= 64, 1 <= L <= 64, W % 4 == 0, P H W < 2^31, B S <= 65535; scale and shift finite, ratio_floor finite and > 0; x / ref 16-byte
+ * aligned, labels 4-byte aligned, labels_bstride 0 or P H W, sums / ws 8-byte aligned; sums, counts, outside and ws overlap neither each
+ * other nor the inputs.  A refused call (IDIFF_E_BADARG) launches nothing and leaves every buffer as it was. */
+int idiff_despeckle_stats(const float* x, const float* ref, const uint8_t* labels, int64_t labels_bstride, int L, float scale, float shift,
+                          float ratio_floor, double* sums, int32_t* counts, int32_t* outside, void* ws, int B, int S, int P, int H, int W,
+                          idiff_stream_t stream);
+int64_t idiff_despeckle_stats_ws_bytes(int B, int S, int L);
 /* Flips and transpositions of image rows (driftSDE self_ensemble): in [R / in_rep][C][H][W] -> out [R][C][H][W].  Row r reads
  * input row r / in_rep under the 3-bit code k = (codes >> 3*((r % S) % period)) & 7: bit 0 = transpose, bit 1 = flip H, bit 2 = flip W,
  * the flips applied after the transposition:

@@ -149,6 +149,8 @@ SIGNATURES = {
     "idiff_region_scores": (I, [P, P, P, I64, I, P, P, P, P, I, I, I64, c_stream]),
     "idiff_region_scores_ws_bytes": (I64, [I, I, I]),
     "idiff_band_labels": (I, [P, P, I64, C.POINTER(C.c_float), I, c_stream]),
+    "idiff_despeckle_stats": (I, [P, P, P, I64, I, F, F, F, P, P, P, P, I, I, I, I, I, c_stream]),
+    "idiff_despeckle_stats_ws_bytes": (I64, [I, I, I]),
     "idiff_dihedral_rows": (I, [P, P, I, I, I, I, I, I, I, C.c_uint32, c_stream]),
     "idiff_tile_gather": (I, [P, P, I, I, I, I, I, I, I, I, P, P, c_stream]),
     "idiff_drift_reverse_step_tiled_dev": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, I, P, U64, U64, U64, c_stream]),

@@ -262,6 +262,145 @@ def region_score_summary(sums, counts, outside, S, names=None, data_range=2.0):
                 invalid=sum(r["invalid"] for r in regions), outside=int(outside.sum()))
 
 
+DESPECKLE_METRICS = ("MEAN", "STD", "ENL", "MEAN_REF", "ENL_REF", "SSI", "SMPI", "MEAN_RATIO", "VAR_RATIO", "ENL_RATIO", "EPI", "LAP_RATIO",
+                     "CNR")
+_FLAT_EPS = 8 * 2.0 ** -53  # despeckle_summary: a variance at or below this share of the sum of squares is rounding, not signal
+
+
+def _moments(n, s1, s2):
+    """n terms with fp64 sums s1 = sum t, s2 = sum t^2 -> (mean, population variance, flat) as exact Fractions of the rounded sums, or None
+    for n = 0 or a non-finite sum.  flat: variance <= 8 * 2^-53 * s2.  Each sum carries at most 2 (n - 1) 2^-53 sum |t| of rounding, which
+    is at most 6 n 2^-53 (s2 / n) on the variance; the factor 8 leaves a margin over that, so a constant region is always flat."""
+    if n <= 0 or not (math.isfinite(s1) and math.isfinite(s2)):
+        return None
+    mean = fractions.Fraction(s1) / n
+    var = fractions.Fraction(s2) / n - mean * mean
+    return mean, var, var <= fractions.Fraction(_FLAT_EPS) * fractions.Fraction(s2)
+
+
+def _root(q):
+    """sqrt of a non-negative Fraction as a float; the quotient is formed exactly first"""
+    return math.sqrt(float(q)) if q > 0 else 0.0
+
+
+def _despeckle_region(s, c):
+    """one region of one row from its 12 sums and 4 counts; CNR is filled in by the caller, which knows the background"""
+    n, n_ratio, n_sten, invalid = (int(v) for v in c)
+    rec = dict(N_PIX=n, N_RATIO=n_ratio, N_STENCIL=n_sten, invalid=invalid, FLAT=None, **{m: None for m in DESPECKLE_METRICS})
+    ma, my = _moments(n, s[0], s[1]), _moments(n, s[2], s[3])
+    if ma is not None:
+        rec.update(MEAN=float(ma[0]), STD=_root(ma[1]), FLAT=bool(ma[2]))
+        if not ma[2]:
+            rec["ENL"] = float(ma[0] * ma[0] / ma[1])
+    if my is not None:
+        rec["MEAN_REF"] = float(my[0])
+        if not my[2]:
+            rec["ENL_REF"] = float(my[0] * my[0] / my[1])
+    if ma is not None and my is not None and not my[2] and ma[1] >= 0:  # zero variance of the reference: no SSI / SMPI
+        if ma[0] != 0 and my[0] != 0:
+            rec["SSI"] = _root((ma[1] / (ma[0] * ma[0])) / (my[1] / (my[0] * my[0]))) * (1.0 if (ma[0] > 0) == (my[0] > 0) else -1.0)
+        rec["SMPI"] = (1.0 + abs(float(my[0] - ma[0]))) * _root(ma[1] / my[1])
+    mr = _moments(n_ratio, s[5], s[6])
+    if mr is not None:
+        rec.update(MEAN_RATIO=float(mr[0]), VAR_RATIO=max(float(mr[1]), 0.0))
+        if not mr[2]:
+            rec["ENL_RATIO"] = float(mr[0] * mr[0] / mr[1])
+    la, ly = _moments(n_sten, s[7], s[9]), _moments(n_sten, s[8], s[10])
+    if la is not None and ly is not None and math.isfinite(s[11]):
+        if not la[2] and not ly[2]:
+            cov = fractions.Fraction(s[11]) / n_sten - la[0] * ly[0]
+            rec["EPI"] = math.copysign(_root(cov * cov / (la[1] * ly[1])), 1.0 if cov >= 0 else -1.0)
+        if s[10] > 0:
+            rec["LAP_RATIO"] = float(fractions.Fraction(s[9]) / fractions.Fraction(s[10]))
+    return rec
+
+
+def _despeckle_rows(sums, counts, who):
+    sums = torch.as_tensor(sums, dtype=torch.float64).detach().cpu()
+    if sums.dim() < 2 or sums.shape[-1] != ops.DESPECKLE_NQ:
+        raise ValueError(f"{who}: sums must be [..., L, {ops.DESPECKLE_NQ}], got {tuple(sums.shape)}")
+    L = int(sums.shape[-2])
+    lead = tuple(sums.shape[:-2])
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64)
+    if tuple(counts.shape) != lead + (L, ops.DESPECKLE_NC):
+        raise ValueError(f"{who}: counts must be {lead + (L, ops.DESPECKLE_NC)} for sums {tuple(sums.shape)}, got {tuple(counts.shape)}")
+    return sums.reshape(-1, L, ops.DESPECKLE_NQ).tolist(), counts.reshape(-1, L, ops.DESPECKLE_NC).tolist(), L, lead
+
+
+def despeckle_summary(sums, counts, outside, names=None, background=0):
+    """The no-reference despeckling statistics from what ops.despeckle_stats returns, on the host:
+        sums [..., L, 12], counts [..., L, 4] (the leading axes, [B, S] from the device, are flattened into rows), outside [B].
+    ->  dict(L, names, background, shape (the leading axes), outside (total),
+        rows      per row a list of one dict per region:
+            N_PIX, N_RATIO, N_STENCIL, invalid   the region's valid / ratio / stencil / invalid pixels
+            MEAN, STD     of a over the valid pixels (population variance);  MEAN_REF  of y
+            FLAT          variance <= 8 * 2^-53 * sum a^2: what is left is the rounding of the sums (see _moments);  ENL is None then
+            ENL           MEAN^2 / variance, the equivalent number of looks;  ENL_REF  that of y
+            SSI           (STD / MEAN) / (STD_ref / MEAN_ref);  SMPI = (1 + |MEAN_ref - MEAN|) STD / STD_ref
+            MEAN_RATIO, VAR_RATIO   of the ratio image rho = y / a over the ratio pixels;  ENL_RATIO = MEAN_RATIO^2 / VAR_RATIO, the
+                          looks of the input when only speckle was removed
+            EPI           the Pearson correlation of La and Ly over the stencil pixels;  LAP_RATIO = sum La^2 / sum Ly^2
+            CNR           |MEAN - MEAN_bg| / sqrt(var + var_bg) against region `background` of the same row
+        regions   per region the mean of each metric over the rows where it is defined and, under "defined", the number of those rows)
+    Rows are not pooled sum with sum: that would carry the images' different means into the variance.  Variances and the EPI's numerator
+    and denominators are combined from the fp64 sums in exact rational arithmetic.  An empty region, a reference of zero variance or a
+    region without a stencil pixel gives None, never a division by zero.  Takes tensors, arrays or nested lists."""
+    s_rows, c_rows, L, lead = _despeckle_rows(sums, counts, "despeckle_summary")
+    outside = torch.as_tensor(outside).detach().cpu().to(torch.int64).reshape(-1)
+    names = [str(i) for i in range(L)] if names is None else [str(n) for n in names]
+    if len(names) != L:
+        raise ValueError(f"despeckle_summary: {len(names)} names for L = {L} regions")
+    if isinstance(background, bool) or not isinstance(background, int) or not 0 <= background < L:
+        raise ValueError(f"despeckle_summary: background must be a region index in [0, {L}), got {background!r}")
+    rows = []
+    for s, c in zip(s_rows, c_rows):
+        recs = [dict(name=names[l], **_despeckle_region(s[l], c[l])) for l in range(L)]
+        mom = [_moments(c[l][0], s[l][0], s[l][1]) for l in range(L)]
+        bg = mom[background]
+        for l in range(L):
+            if mom[l] is not None and bg is not None:
+                den = max(mom[l][1], 0) + max(bg[1], 0)
+                if den > 0:
+                    d = mom[l][0] - bg[0]
+                    recs[l]["CNR"] = _root(d * d / den)
+        rows.append(recs)
+    regions = []
+    for l in range(L):
+        rec = dict(name=names[l], N_PIX=sum(r[l]["N_PIX"] for r in rows), invalid=sum(r[l]["invalid"] for r in rows), defined={})
+        for m in DESPECKLE_METRICS:
+            have = [r[l][m] for r in rows if r[l][m] is not None]
+            rec[m] = math.fsum(have) / len(have) if have else None
+            rec["defined"][m] = len(have)
+        regions.append(rec)
+    return dict(L=L, names=names, background=background, shape=list(lead), rows=rows, regions=regions, outside=int(outside.sum()))
+
+
+def homogeneous_cells(sums, counts, share=0.25):
+    """The customary "ENL in homogeneous regions" without a hand-drawn map: per row of ops.despeckle_stats' record (over a grid of cells,
+    ops.grid_labels) the ceil(share * non-empty cells) cells with the lowest coefficient of variation of the *reference* (compared as
+    exact rationals; ties go to the lower index; a cell whose reference mean is 0 ranks last) -> dict(cells: per row the chosen region
+    indices in rank order, ENL_AUTO: per row the mean ENL of the restored rows over the chosen cells where it is defined, else None)."""
+    if isinstance(share, bool) or not isinstance(share, numbers.Real) or not 0 < share <= 1:
+        raise ValueError(f"homogeneous_cells: share must be in (0, 1], got {share!r}")
+    s_rows, c_rows, L, _ = _despeckle_rows(sums, counts, "homogeneous_cells")
+    cells, auto = [], []
+    for s, c in zip(s_rows, c_rows):
+        ranked = []
+        for l in range(L):
+            my = _moments(c[l][0], s[l][2], s[l][3])
+            if my is None:
+                continue
+            cv2 = max(my[1], 0) / (my[0] * my[0]) if my[0] != 0 else None
+            ranked.append((cv2 is None, cv2 if cv2 is not None else 0, l))
+        ranked.sort()
+        k = max(1, math.ceil(share * len(ranked) - 1e-9)) if ranked else 0  # 0.1 * 10 is one cell, whatever the product's last bit
+        chosen = [l for _, _, l in ranked[:k]]
+        enl = [e for e in (_despeckle_region(s[l], c[l])["ENL"] for l in chosen) if e is not None]
+        cells.append(chosen)
+        auto.append(math.fsum(enl) / len(enl) if enl else None)
+    return dict(cells=cells, ENL_AUTO=auto)
+
+
 def _sparsification_K(K):
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= ops.SPARSIFICATION_MAX_K:
         raise ValueError(f"sparsification: K must be an int in [1, {ops.SPARSIFICATION_MAX_K}], got {K!r}")
@@ -1656,6 +1795,27 @@ class driftSDE:
         if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) not in (tuple(target.shape), tuple(target.shape[1:])):
             raise ValueError(f"region_scores: labels must be a uint8 tensor of shape {tuple(target.shape)} or {tuple(target.shape[1:])}")
         return ops.region_scores(x.contiguous(), target.contiguous(), labels.contiguous(), L)
+
+    @staticmethod
+    def despeckle_stats(samples_or_output, ref, labels, L):
+        """The sums behind the no-reference despeckling statistics per region of a uint8 label map: samples [B, S, C, H, W] (or one
+        restoration [B, C, H, W], S = 1) against ref [B, C, H, W] (the noisy input, or the target), labels [B, C, H, W] or one shared
+        [C, H, W] -> (sums float64 [B, S, L, 12], counts int32 [B, S, L, 4], outside int32 [B]) on the device, from one
+        ops.despeckle_stats call (two launches, no host copy) on the [0, 1] intensity scale; despeckle_summary(sums, counts, outside) reads
+        ENL / SSI / SMPI / MEAN_RATIO / VAR_RATIO / EPI / LAP_RATIO / CNR off them, homogeneous_cells(sums, counts) the ENL of the most
+        homogeneous cells of a grid."""
+        x = samples_or_output
+        if not torch.is_tensor(ref) or ref.dim() != 4:
+            raise ValueError("despeckle_stats: ref must be a [B, C, H, W] tensor")
+        want = (tuple(ref.shape), tuple(ref.shape[:1]) + (x.shape[1] if torch.is_tensor(x) and x.dim() > 1 else 0,) + tuple(ref.shape[1:]))
+        if not torch.is_tensor(x) or tuple(x.shape) not in want:
+            raise ValueError(f"despeckle_stats: samples must be [B, S, C, H, W] or [B, C, H, W] for ref {tuple(ref.shape)}, got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) not in (tuple(ref.shape), tuple(ref.shape[1:])):
+            raise ValueError(f"despeckle_stats: labels must be a uint8 tensor of shape {tuple(ref.shape)} or {tuple(ref.shape[1:])}")
+        if ref.shape[-1] % 4:
+            raise ValueError(f"despeckle_stats: the image width must be a multiple of 4, got {int(ref.shape[-1])}")
+        return ops.despeckle_stats(x.contiguous(), ref.contiguous(), labels.contiguous(), L)
 
     @staticmethod
     def sparsification(output, uncertainty, target, K=20):

@@ -397,6 +397,36 @@ class CLIPDriftModel():
             labels = labels[None].expand(self.target.shape[1], -1, -1)
         return self.sde.region_scores(held, self.target, labels.contiguous(), L)
 
+    def despeckle_stats(self, labels, L, what="ensemble", against="input"):
+        """the sums behind the no-reference despeckling statistics per region of a uint8 label map, of what test() left
+        (driftSDE.despeckle_stats) -> (sums [B, S, L, 12], counts [B, S, L, 4], outside [B]) on the device.  what: as in region_scores
+        ("ensemble": the members in self.samples; "output": self.output, S = 1; "median": output_median).  against: "input", the noisy
+        image the chain started from (needs no ground truth), or "target".  labels: [B, C, H, W], one shared [C, H, W], or [H, W], which is
+        expanded over the channels; a label >= L (255 by convention) keeps its pixel out of every region."""
+        if what not in ("ensemble", "output", "median"):
+            raise ValueError(f'despeckle_stats: what must be "ensemble", "output" or "median", got {what!r}')
+        if against not in ("input", "target"):
+            raise ValueError(f'despeckle_stats: against must be "input" or "target", got {against!r}')
+        if getattr(self, "output", None) is None:
+            raise ValueError("despeckle_stats: no output is held; run test() first")
+        if what == "ensemble":
+            if getattr(self, "samples", None) is None:
+                raise ValueError("despeckle_stats: no samples are held; run test(return_samples=True) with the sde's num_samples > 1 first")
+            held = self.samples
+        elif what == "median":
+            if getattr(self, "output_median", None) is None:
+                raise ValueError("despeckle_stats: no median map is held; run test(return_samples=True) with the sde's interval set first")
+            held = self.output_median
+        else:
+            held = self.output
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8:
+            raise ValueError("despeckle_stats: labels must be a uint8 tensor")
+        ref = self.input if against == "input" else self.target
+        labels = labels.to(ref.device)
+        if labels.dim() == 2:
+            labels = labels[None].expand(ref.shape[1], -1, -1)
+        return self.sde.despeckle_stats(held, ref, labels.contiguous(), L)
+
     def power_spectra(self, with_target=True):
         """radial power spectra of what test() left (driftSDE.power_spectra): of the members in self.samples and their mean after
         test(return_samples=True), else of self.output (the plain chain: S = 1), against self.target when with_target -> a dict of

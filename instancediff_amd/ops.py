@@ -1169,6 +1169,43 @@ def grid_labels(H, W, gy, gx, device="cpu"):
     return _grid_labels_dev(H, W, gy, gx, str(torch.device(device)))
 
 
+DESPECKLE_NQ = 12  # sum a, a^2, y, y^2, a y | rho, rho^2 | La, Ly, La^2, Ly^2, La Ly
+DESPECKLE_NC = 4   # valid, ratio, stencil, invalid
+
+
+def despeckle_stats(x, ref, labels, L, scale=0.5, shift=0.5, ratio_floor=2.0 ** -8):
+    """x [B, S, C, H, W] (the samples of an ensemble) or [B, C, H, W] (one restoration, S = 1), ref [B, C, H, W] (the noisy input, or the
+    target), labels uint8 [B, C, H, W] or one shared [C, H, W], L regions -> (sums float64 [B, S, L, 12], counts int32 [B, S, L, 4],
+    outside int32 [B]), all on the device: the sums behind the no-reference despeckling statistics per region and member.  With
+    a = x scale + shift and y = ref scale + shift (the defaults put [-1, 1] tensors on the [0, 1] intensity scale, on which speckle is
+    multiplicative): sum a, a^2, y, y^2, a y over the region's valid pixels (a and y finite); sum rho, rho^2 of the ratio image
+    rho = y / a where a >= ratio_floor; sum La, Ly, La^2, Ly^2, La Ly of the 4-neighbour Laplacians where the whole stencil is valid
+    and inside the plane.  counts = valid, ratio, stencil and invalid pixels; outside = pixels with a label >= L.  Two launches, no host
+    copy; include/idiff.h states the arithmetic and the order.  models/SDEs/driftSDE.py's despeckle_summary turns the record into
+    ENL / SSI / SMPI / MEAN_RATIO / VAR_RATIO / EPI / LAP_RATIO / CNR."""
+    lib = _lib.load()
+    _c(x, "x"), _c(ref, "ref"), _c(labels, "labels", torch.uint8)
+    if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= REGION_MAX_L:
+        raise _lib.IdiffError(f"despeckle_stats: L must be an int in [1, {REGION_MAX_L}], got {L!r}")
+    assert ref.dim() == 4, "despeckle_stats: ref is [B, C, H, W]"
+    if x.dim() == 4:
+        x = x.unsqueeze(1)
+    assert x.dim() == 5, "despeckle_stats: x is [B, S, C, H, W] or [B, C, H, W]"
+    B, S = x.shape[:2]
+    assert tuple(ref.shape) == (B,) + tuple(x.shape[2:]), "despeckle_stats: ref is x without the member axis"
+    shared = tuple(labels.shape) == tuple(ref.shape[1:])
+    assert shared or tuple(labels.shape) == tuple(ref.shape), "despeckle_stats: labels has the shape of ref, or of one image of it"
+    P, H, W = (int(n) for n in ref.shape[1:])
+    sums = torch.empty((B, S, L, DESPECKLE_NQ), device=x.device, dtype=torch.float64)
+    counts = torch.empty((B, S, L, DESPECKLE_NC), device=x.device, dtype=torch.int32)
+    outside = torch.empty((B,), device=x.device, dtype=torch.int32)
+    ws = torch.empty((max(int(lib.idiff_despeckle_stats_ws_bytes(B, S, L)), 8) // 8,), device=x.device, dtype=torch.float64)
+    check(lib.idiff_despeckle_stats(_p(x), _p(ref), _p(labels), 0 if shared else P * H * W, L, float(scale), float(shift), float(ratio_floor),
+                                    C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(outside.data_ptr()),
+                                    C.c_void_p(ws.data_ptr()), B, S, P, H, W, _stream()), "despeckle_stats")
+    return sums, counts, outside
+
+
 @functools.lru_cache(maxsize=16)
 def radial_bins(H, W):
     """The radial frequency bins of an H x W image's half plane, on the host in exact integer arithmetic -> (bins int32 [H, Wh], counts

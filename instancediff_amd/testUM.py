@@ -37,7 +37,13 @@ With `--regions SPEC` the scores are also taken per region of a label map, on th
 restoration itself): `bands:e1,e2,...` labels every pixel by the intensity band of its ground truth (edges on the x/2 + 0.5 scale),
 `grid:GYxGX` by the cell of a GY x GX grid, `file` by the raw uint8 map the dataset item's optional `"label"` key names (`--regions-L L`
 regions; any label >= L, 255 by convention, is outside).  Per image `RMSE_r`, `CRPS_r` (the MAE at S = 1), `BIAS_r` (x/2 + 0.5 scale) and
-`SSR_r` are listed region by region; the pooled record per artifact type goes to `regions.json`.  Sampling shards by image across ranks when launched with torchrun.
+`SSR_r` are listed region by region; the pooled record per artifact type goes to `regions.json`.
+With `--speckle [SPEC]` (the `--regions` grammar, default `grid:8x8`; `--speckle-L L` with `file`, `--speckle-background l` for the CNR) the
+restoration is judged without a ground truth, on the device and on the x/2 + 0.5 scale, from the restored image and the noisy input alone:
+per image `ENL` (the equivalent number of looks, the mean over the regions), `ENL_AUTO` (over the quarter of the regions in which the input
+is most homogeneous), `SSI`, `MEAN_RATIO` / `VAR_RATIO` of the ratio image input / restored, and the edge-preservation index against the input
+(`EPI_in`) and the ground truth (`EPI_gt`); with `--num-samples S` also `ENL_member` / `LAP_RATIO_member` beside the mean image's `ENL` /
+`LAP_RATIO` (how much smoother the mean is than a draw); the means over a type's images go to `speckle.json`.  Sampling shards by image across ranks when launched with torchrun.
 """
 import argparse
 import json
@@ -53,8 +59,8 @@ from . import ops, parallel
 from .data import create_dataset, dump_raw, iterate_batches
 from .models import create_model
 from .models.SDEs import create_sde
-from .models.SDEs.driftSDE import (ensemble_distance_summary, ensemble_mode_summary, ensemble_score_summary, region_score_summary,
-                                   sparsification_summary, spectrum_summary)
+from .models.SDEs.driftSDE import (despeckle_summary, ensemble_distance_summary, ensemble_mode_summary, ensemble_score_summary,
+                                   homogeneous_cells, region_score_summary, sparsification_summary, spectrum_summary)
 
 
 def pool_spectra(entries, S):
@@ -134,6 +140,15 @@ def build_parser():
                              "--regions-L); RMSE_r / CRPS_r / BIAS_r / SSR_r per image and regions.json per artifact type")
     parser.add_argument("--regions-L", type=int, default=argparse.SUPPRESS, metavar="L", dest="regions_L",
                         help="the number of regions of --regions file: labels 0 .. L-1 count, any other label (255 by convention) is outside")
+    parser.add_argument("--speckle", type=str, nargs="?", const="grid:8x8", default=argparse.SUPPRESS, metavar="SPEC",
+                        help="no-reference despeckling statistics per region of a label map (the --regions grammar, default grid:8x8), with or "
+                             "without num_samples: ENL / ENL_AUTO / SSI / MEAN_RATIO / VAR_RATIO / EPI_in / EPI_gt per image (with num_samples "
+                             "also ENL_member / LAP_RATIO_member) and speckle.json per artifact type; an image whose width is not a multiple "
+                             "of 4 is left out, with a note on its line")
+    parser.add_argument("--speckle-L", type=int, default=argparse.SUPPRESS, metavar="L", dest="speckle_L",
+                        help="the number of regions of --speckle file")
+    parser.add_argument("--speckle-background", type=int, default=argparse.SUPPRESS, metavar="l", dest="speckle_background",
+                        help="the background region of the contrast-to-noise ratio (default 0)")
     return parser
 
 
@@ -191,6 +206,39 @@ def _scaled(v, scale):
     return None if v is None else scale * v
 
 
+def parse_speckle(spec, speckle_L=None, background=None):
+    """--speckle SPEC (and --speckle-L, --speckle-background) -> parse_regions' dict plus background.  Raises ValueError with the message
+    parser.error prints."""
+    try:
+        speckle = parse_regions(spec, speckle_L)
+    except ValueError as e:
+        raise ValueError(str(e).replace("--regions", "--speckle")) from None
+    background = 0 if background is None else background
+    if isinstance(background, bool) or not isinstance(background, int) or not 0 <= background < speckle["L"]:
+        raise ValueError(f"--speckle-background takes a region index in [0, {speckle['L']}), got {background!r}")
+    speckle["background"] = background
+    return speckle
+
+
+def _region_mean(rows, metric):
+    """the mean of a metric over every row and region of a despeckle_summary where it is defined, else None"""
+    have = [q[metric] for row in rows for q in row if q[metric] is not None]
+    return math.fsum(have) / len(have) if have else None
+
+
+def speckle_record(recs, speckle):
+    """the speckle.json record of a type: recs = per image dict(input, target[, members]) of ops.despeckle_stats' host tensors"""
+    out = dict(spec=speckle["spec"], L=speckle["L"], names=speckle["names"], background=speckle["background"], images=len(recs))
+    for key in ("input", "target", "members"):
+        if not all(key in rec for rec in recs):
+            continue
+        one = despeckle_summary(*(torch.cat([rec[key][q] for rec in recs]) for q in range(3)), speckle["names"], speckle["background"])
+        auto = [a for a in homogeneous_cells(*(torch.cat([rec[key][q] for rec in recs]) for q in range(2)))["ENL_AUTO"] if a is not None]
+        out[key] = dict(regions=one["regions"], outside=one["outside"], ENL_AUTO=math.fsum(auto) / len(auto) if auto else None,
+                        **{m: _region_mean(one["rows"], m) for m in ("ENL", "SSI", "MEAN_RATIO", "VAR_RATIO", "EPI", "LAP_RATIO")})
+    return out
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -223,6 +271,14 @@ def main(argv=None):
             parser.error("--regions-L goes with --regions file")
         try:
             regions = parse_regions(args.regions, getattr(args, "regions_L", None))
+        except ValueError as e:
+            parser.error(str(e))
+    speckle = None
+    if any(hasattr(args, a) for a in ("speckle", "speckle_L", "speckle_background")):  # refused before the model is built, like --regions
+        if not hasattr(args, "speckle"):
+            parser.error("--speckle-L and --speckle-background go with --speckle")
+        try:
+            speckle = parse_speckle(args.speckle, getattr(args, "speckle_L", None), getattr(args, "speckle_background", None))
         except ValueError as e:
             parser.error(str(e))
     rank, world, local = parallel.init_distributed()
@@ -296,6 +352,9 @@ def main(argv=None):
     if regions is not None:
         for r in results.values():
             r['regions'] = []
+    if speckle is not None:
+        for r in results.values():
+            r['speckle'] = []
     times = []
     n_done = n_replayed = 0
     for phase, dataset_opt in sorted(opt["datasets"].items()):
@@ -409,6 +468,22 @@ def main(argv=None):
                     r['regions'].append(rec)
                     extra += (f", RMSE_r={[_scaled(q['RMSE'], 0.5) for q in one]}, CRPS_r={[_scaled(q['CRPS'], 0.5) for q in one]}, "
                               f"BIAS_r={[_scaled(q['BIAS'], 0.5) for q in one]}, SSR_r={[q['SSR'] for q in one]}")
+                if speckle is not None and model.output.shape[-1] % 4:  # the kernel reads aligned 16-byte pieces of an image line
+                    extra += ", ENL=left out (W is not a multiple of 4)"
+                elif speckle is not None:  # a = x/2 + 0.5 inside the kernel: RMSE's scale, on which speckle is multiplicative
+                    labels = region_labels(speckle, model, it)
+                    rec = {key: [t.cpu() for t in model.despeckle_stats(labels, speckle["L"], what="output", against=key)]
+                           for key in ("input", "target")}
+                    if S > 1:
+                        rec["members"] = [t.cpu() for t in model.despeckle_stats(labels, speckle["L"], what="ensemble", against="input")]
+                    r['speckle'].append(rec)
+                    one = speckle_record([rec], speckle)
+                    extra += (f", ENL={one['input']['ENL']}, ENL_AUTO={one['input']['ENL_AUTO']}, SSI={one['input']['SSI']}, "
+                              f"MEAN_RATIO={one['input']['MEAN_RATIO']}, VAR_RATIO={one['input']['VAR_RATIO']}, EPI_in={one['input']['EPI']}, "
+                              f"EPI_gt={one['target']['EPI']}")
+                    if S > 1:
+                        extra += (f", ENL_member={one['members']['ENL']}, LAP_RATIO={one['input']['LAP_RATIO']}, "
+                                  f"LAP_RATIO_member={one['members']['LAP_RATIO']}")
                 print(f' Testing {i}, {it["GT_path"]}: RMSE={rmse}, SSIM={ssim}, PSNR={psnr}' + extra)
                 n_done += 1
                 if args.limit and n_done >= args.limit:
@@ -454,6 +529,18 @@ def main(argv=None):
             with open(os.path.join(result_root, k, "regions.json"), "w") as f:  # CRPS / RMSE / BIAS on RMSE's x/2 + 0.5 scale
                 json.dump(dict(spec=regions["spec"], S=S, L=pooled["L"], names=pooled["names"], images=len(v['regions']),
                                regions=pooled["regions"], N_PIX=pooled["N_PIX"], invalid=pooled["invalid"], outside=pooled["outside"]), f)
+    if speckle is not None:  # the type's record: the mean of each metric over its images (not pooled sums: the images' means differ)
+        for k, v in results.items():
+            if not v['num'] or not v['speckle']:
+                continue
+            pooled = speckle_record(v['speckle'], speckle)
+            v['pooled_speckle'] = pooled
+            print(f"{k}, speckle ({speckle['spec']}) over {len(v['speckle'])} images: "
+                  + ", ".join(f"{m}: {pooled['input'][m]}" for m in ("ENL", "ENL_AUTO", "SSI", "MEAN_RATIO", "VAR_RATIO", "LAP_RATIO"))
+                  + f", EPI_in: {pooled['input']['EPI']}, EPI_gt: {pooled['target']['EPI']}"
+                  + (f", ENL_member: {pooled['members']['ENL']}, LAP_RATIO_member: {pooled['members']['LAP_RATIO']}" if S > 1 else ""))
+            with open(os.path.join(result_root, k, "speckle.json"), "w") as f:
+                json.dump(dict(S=S, **pooled), f)
     if K_modes is not None:  # the type's record: the spectra added mode by mode over its images, not the mean of the per-image ratios
         for k, v in results.items():
             if not v['num'] or not v['modes']:
